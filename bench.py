@@ -9,6 +9,11 @@ trials (synthetic BSC keys) are generated before timing and are resident in HBM.
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c1|c4]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 
+A plain run sets up, warms up, times the K steps and prints the line.  `--full`
+adds what takes runs of its own: the warm trial-generation call, the serial
+decode launches behind decode_kernel_ms and the roofline, and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
+
 One process per GPU.  `--gpus N > 1` without a launcher starts the N ranks
 itself (child processes, before this process touches the GPU) with the same
 environment torchrun would give them; under a launcher WORLD_SIZE must equal
@@ -100,11 +105,17 @@ def main():
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the steps alternate over: step i+1's frames start on CUs freed by "
                          "step i's last frames (1 = strictly serial steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the warm trial-generation call, "
+                         "the serial roofline launches (decode_kernel_ms) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (bits, iterations, synd_ok, "
+                         "key_match) as DIR/<name>.npy, float32")
     ap.add_argument("--roofline-launches", type=int, default=3,
-                    help="serial decode launches after the timed region, timed alone for the roofline (with "
-                         "--streams > 1 a timed step's decode shares CUs with its neighbours)")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: serial decode launches after the timed region, timed alone for the roofline "
+                         "(with --streams > 1 a timed step's decode shares CUs with its neighbours)")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0, help="with --full")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--c5-point", type=int, default=-1,
                     help="with --workload c5ra: one of the 26 C5 sweep points (C5_POINTS index)")
     ap.add_argument("--share-device", action="store_true",
@@ -192,15 +203,16 @@ def main():
 
     # untimed by the metric (the reference's window starts after run_trial's
     # keys exist, src/simulation.cpp:559); reported: the first call (it also
-    # builds the generator's jump table) and a warm call
+    # builds the generator's jump table) and, with --full, a warm call (it
+    # writes the same trials again)
     gen_s = []
-    for _ in range(2):
+    for _ in range(2 if args.full else 1):
         torch.cuda.synchronize()
         tg0 = time.perf_counter()
         q_acc = generate()
         torch.cuda.synchronize()
         gen_s.append(time.perf_counter() - tg0)
-    trial_gen_first_s, trial_gen_s = gen_s
+    trial_gen_first_s, trial_gen_s = gen_s[0], (gen_s[1] if args.full else None)
     lp = Q.log_p(q_acc)
     tlp = torch.full((batch,), lp, dtype=torch.float64, device=dev)
     nst = max(1, args.streams)
@@ -254,11 +266,14 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     step_ms_stream = float(np.mean([ev0[i].elapsed_time(ev1[i]) for i in range(args.steps)]))
-    # Roofline: the decode kernel alone — a few serial steps on one stream with
-    # the library's kernel timing on (HIP events around the decode kernel
-    # launch only, on the stream it runs on), outside the timed region.
+    last = slots[(args.steps - 1) % nst]  # every step decodes the same trials
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
+    # Roofline (--full): the decode kernel alone — a few serial steps on one
+    # stream with the library's kernel timing on (HIP events around the decode
+    # kernel launch only, on the stream it runs on), outside the timed region.
     kernel_ms = None
-    if args.roofline_launches > 0:
+    if args.full and args.roofline_launches > 0:
         g.set_kernel_timing(True)
         kms = []
         for j in range(args.roofline_launches):
@@ -268,7 +283,6 @@ def main():
         kernel_ms = float(np.mean(kms))
         # (the roofline steps decode the same trials as the timed ones)
 
-    last = slots[(args.steps - 1) % nst]  # every step decodes the same trials
     it_sum = int(last.iters.to(torch.int64).sum().item())
     n_ok = int(last.ok.to(torch.int64).sum().item())
     n_keys = int(last.km.to(torch.int64).sum().item())
@@ -366,7 +380,7 @@ def main():
                 # VALU issue, and the byte model is kept beside it.
                 res["hbm_model_roofline"] = res["roofline"]
                 res["roofline"] = dict(res["compute_roofline"], traffic=traffic)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(H, alg, prim, sec, qber, args.max_iterations,
                                                args.cpu_baseline_seconds, k_info,
                                                SIMULATION_SEEDS.get(args.workload, 1022025) + 1,
@@ -375,6 +389,30 @@ def main():
     if dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BITS_BYTES = 56_000_000  # of the 64 MB a dump may take; the per-frame arrays are a few KB
+
+
+def dump_outputs(directory, slot, rank: int, world: int) -> None:
+    """Write the outputs the timed path left in `slot` (its last timed step;
+    the stream is idle by now) as float32 <name>.npy files: per frame the
+    decoder's iteration count, its syndrome flag and the key comparison, and
+    the decoded bits.  When the bits exceed DUMP_BITS_BYTES as float32, a
+    fixed seeded sample of frames is written and bits_frames.npy names them.
+    With more than one rank each writes its own <name>.rank<r>.npy."""
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    batch, n = slot.bits.shape
+    rows = min(batch, max(1, DUMP_BITS_BYTES // (4 * n)))
+    frames = np.arange(batch) if rows == batch else np.sort(np.random.default_rng(20251).choice(batch, rows, False))
+    bits = slot.bits[torch.from_numpy(frames).to(slot.bits.device)]
+    out = {"iterations": slot.iters, "synd_ok": slot.ok, "key_match": slot.km, "bits": bits,
+           "bits_frames": torch.from_numpy(frames)}
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, t in out.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), t.cpu().numpy().astype(np.float32))
 
 
 def check_devices(have: int, need: int, shared: bool) -> None:

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_contract(gpu_available):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--batch", "256",
-                        "--steps", "3", "--warmup", "1", "--cpu-baseline-seconds", "1"],
+                        "--steps", "3", "--warmup", "1", "--full", "--cpu-baseline-seconds", "1"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -41,3 +41,37 @@ def test_bench_line_contract(gpu_available):
     assert cb["value"] > 0 and cb["unit"] == "info-bits/s" and cb["cores"] >= 1 and cb["kind"] in ("port", "reference")
     assert cb["sample"]
     assert 0.0 <= d["fer"] <= 1.0 and d["mean_iterations"] >= 1.0
+    assert d["decode_kernel_ms"] > 0 and d["trial_generation_s"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs(gpu_available, tmp_path):
+    """Without --full the run times its steps and prints the line (no serial
+    roofline launches, no CPU baseline); --dump-outputs writes the last timed
+    step's outputs as float32 .npy files that agree with the line's counters."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--batch", "256",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["cpu_baseline"] is None and d["decode_kernel_ms"] is None and d["trial_generation_s"] is None
+    assert d["roofline"]["achieved"] > 0
+    n = d["config"]["n"]
+    got = {p.name: np.load(p) for p in out.iterdir()}
+    assert sorted(got) == ["bits.npy", "bits_frames.npy", "iterations.npy", "key_match.npy", "synd_ok.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    assert got["bits.npy"].shape == (256, n) and np.array_equal(got["bits_frames.npy"], np.arange(256))
+    assert set(np.unique(got["bits.npy"])) <= {0.0, 1.0}
+    for k in ("iterations.npy", "synd_ok.npy", "key_match.npy"):
+        assert got[k].shape == (256,)
+    assert d["mean_iterations"] == pytest.approx(got["iterations.npy"].mean(), rel=1e-6)
+    assert d["fer"] == pytest.approx(1.0 - got["synd_ok.npy"].mean(), abs=1e-9)
+    assert d["key_mismatch_rate"] == pytest.approx(1.0 - got["key_match.npy"].mean(), abs=1e-9)

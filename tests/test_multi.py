@@ -246,7 +246,8 @@ def _bench_line(args, env=None, launcher=False):
     return json.loads(lines[0])
 
 
-_SMALL = ["--workload", "c1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--roofline-launches", "1"]
+_SMALL = ["--workload", "c1", "--steps", "2", "--warmup", "1",
+          "--full", "--no-cpu-baseline", "--roofline-launches", "1"]
 
 
 @pytest.mark.gpu

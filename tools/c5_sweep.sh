@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 B=${BATCH:-4096}
 O=gpurun_out/c5sweep${BATCH:+_b$BATCH}; mkdir -p $O
 for i in $(seq 0 25); do
-  timeout -k 10 120 python bench.py --workload c5ra --c5-point $i --batch $B --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline \
+  timeout -k 10 120 python bench.py --full --workload c5ra --c5-point $i --batch $B --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline \
       --roofline-launches 1 > $O/point_$i.json 2> $O/point_$i.err || { tail -5 $O/point_$i.err; exit 3; }
   echo "point $i done"
 done

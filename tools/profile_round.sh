@@ -20,7 +20,7 @@ pass() {  # name, bench args, rocprof args...
   if [ $rc -ne 0 ]; then echo "pass $name failed rc=$rc" >&2; tail -20 "$OUT/$name.log" >&2; exit $rc; fi
 }
 if [ "${DEFAULT:-1}" = 1 ]; then
-  pass default_trace "" --kernel-trace --stats
+  pass default_trace "--full" --kernel-trace --stats
 fi
 for wl in ${WLS:-c2 c3}; do
   B="--workload $wl --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline --streams 1 --roofline-launches 0"

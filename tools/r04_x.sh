@@ -12,7 +12,7 @@ tail -3 $O/pytest_split.log
 for rep in 1 2; do
   for x in 1 0; do
     for wl in c4 c4g; do
-      QLDPC_SPLIT_X=$x timeout -k 10 200 python bench.py --workload $wl --no-cpu-baseline --steps 5 > $O/b_${wl}_x${x}_$rep.json 2> $O/b_${wl}_x${x}_$rep.err || exit 12
+      QLDPC_SPLIT_X=$x timeout -k 10 200 python bench.py --full --workload $wl --no-cpu-baseline --steps 5 > $O/b_${wl}_x${x}_$rep.json 2> $O/b_${wl}_x${x}_$rep.err || exit 12
       python - $O/b_${wl}_x${x}_$rep.json $x <<'PY'
 import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[1].split('/')[-1], "Gbit/s", round(d["value"]/1e9,4), "dec ms", round(d["decode_kernel_ms"],3), "iters", d["mean_iterations"], "fer", d["fer"])

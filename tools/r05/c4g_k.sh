@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 O=gpurun_out/r05_c4gk; mkdir -p $O
 for K in 11 16 12; do
-  QLDPC_SPLIT_K=$K timeout -k 10 300 python bench.py --workload c4g --steps 4 --warmup 1 --no-cpu-baseline > $O/k$K.json 2> $O/k$K.err || { tail -5 $O/k$K.err; exit 3; }
+  QLDPC_SPLIT_K=$K timeout -k 10 300 python bench.py --full --workload c4g --steps 4 --warmup 1 --no-cpu-baseline > $O/k$K.json 2> $O/k$K.err || { tail -5 $O/k$K.err; exit 3; }
   python3 -c "
 import json; d=json.load(open('$O/k$K.json'))
 print('K=$K decode', round(d['decode_kernel_ms'],2), 'step', round(d['ms_per_step'],2), 'iters', round(d['mean_iterations'],3), 'lanes', d['config']['lanes_per_frame'])"

@@ -22,5 +22,5 @@ PY
 M=tests/golden/matrices/c2_n10240_m2201.alist.gz
 timeout -k 10 240 tests/dropin/batch_check time $M 1 0 0 0 0.0215 50 4096 1022025 0 > $O/seam_c2.txt 2>&1 || { cat $O/seam_c2.txt; exit 12; }
 echo "seam c2: $(cat $O/seam_c2.txt)"
-timeout -k 10 300 python bench.py --workload c2 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err || { tail -5 $O/bench_c2.err; exit 11; }
+timeout -k 10 300 python bench.py --full --workload c2 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err || { tail -5 $O/bench_c2.err; exit 11; }
 python -c "import json;d=json.load(open('$O/bench_c2.json'));print('c2', round(d['value']/1e9,3), 'Gbit/s', round(d['ms_per_step'],2), 'ms/step gen', round(d['trial_generation_s']*1e3,3))"

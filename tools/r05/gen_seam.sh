@@ -12,7 +12,7 @@ timeout -k 10 1000 python -u -m pytest -x -v --timeout 300 --timeout-method thre
 tail -3 $O/pytest.log
 fi
 for w in c2 c4 c4g c5 c5ra; do
-  timeout -k 10 300 python bench.py --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || { tail -5 $O/bench_$w.err; exit 11; }
+  timeout -k 10 300 python bench.py --full --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || { tail -5 $O/bench_$w.err; exit 11; }
   python -c "import json;d=json.load(open('$O/bench_$w.json'));print('$w', round(d['value']/1e9,3), 'Gbit/s', round(d['ms_per_step'],2), 'ms/step gen', round(d['trial_generation_s']*1e3,3), 'ms first', round(d['trial_generation_first_call_s']*1e3,1))"
 done
 M=tests/golden/matrices/c2_n10240_m2201.alist.gz

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for arm in prod scanhot; do
   for wl in c4 c4g; do
     if [ $arm = prod ]; then unset QLDPC_AB_BUILD; else export QLDPC_AB_BUILD=$arm; fi
-    timeout -k 10 300 python bench.py --workload $wl --steps 4 --warmup 1 --no-cpu-baseline --streams 1 > $O/${arm}_${wl}_$rep.json 2> $O/${arm}_${wl}_$rep.err || { tail -5 $O/${arm}_${wl}_$rep.err; exit 3; }
+    timeout -k 10 300 python bench.py --full --workload $wl --steps 4 --warmup 1 --no-cpu-baseline --streams 1 > $O/${arm}_${wl}_$rep.json 2> $O/${arm}_${wl}_$rep.err || { tail -5 $O/${arm}_${wl}_$rep.err; exit 3; }
     python3 -c "
 import json; d=json.load(open('$O/${arm}_${wl}_$rep.json'))
 it=d['mean_iterations']*d['config']['batch_per_gpu']

@@ -17,7 +17,7 @@ for rep in 1 2 3; do
   timeout -k 10 240 tests/dropin/batch_check sweep $M4 1 0 0 0 $O/q_c4.txt 50 128 1022025 >> $O/sweep_c4.txt 2>&1 || exit 15
 done
 for w in c2 c5 c4; do
-  timeout -k 10 300 python bench.py --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || exit 11
+  timeout -k 10 300 python bench.py --full --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || exit 11
   python -c "import json;d=json.load(open('$O/bench_$w.json'));print('bench $w', round(d['ms_per_step'],2), 'ms/step')"
 done
 cat $O/seam_c2.txt $O/sweep_c2.txt $O/sweep_c5.txt $O/sweep_c4.txt

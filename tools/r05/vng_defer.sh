@@ -10,7 +10,7 @@ tail -1 $O/pytest.log
 run() {  # arm label args...
   local arm=$1 lab=$2; shift 2
   if [ $arm = prod ]; then unset QLDPC_AB_BUILD; else export QLDPC_AB_BUILD=$arm; fi
-  timeout -k 10 300 python bench.py "$@" --steps 4 --warmup 1 --no-cpu-baseline > $O/${arm}_${lab}.json 2> $O/${lab}.err || { tail -5 $O/${lab}.err; exit 3; }
+  timeout -k 10 300 python bench.py --full "$@" --steps 4 --warmup 1 --no-cpu-baseline > $O/${arm}_${lab}.json 2> $O/${lab}.err || { tail -5 $O/${lab}.err; exit 3; }
   python3 -c "
 import json; d=json.load(open('$O/${arm}_${lab}.json'))
 print('$arm $lab', round(d['value']/1e9,4), 'Gbit/s decode', round(d['decode_kernel_ms'],2), 'step', round(d['ms_per_step'],2), 'iters', round(d['mean_iterations'],3), 'fer', d['fer'])"

@@ -8,11 +8,11 @@ cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 O=gpurun_out/r06_c5_512; mkdir -p $O
 T="timeout -k 10 180"
 export TMPDIR=/tmp
-$T python bench.py --workload c5ra --batch 512 --steps 40 --warmup 3 > $O/bench_c5ra_b512.json 2> $O/bench_c5ra_b512.err || exit 3
-$T python bench.py --workload c5ra --batch 512 --steps 40 --warmup 3 --streams 1 --no-cpu-baseline > $O/bench_c5ra_b512_s1.json 2> $O/bench_c5ra_b512_s1.err || exit 3
-$T python bench.py --workload c5ra --batch 4096 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c5ra_b4096.json 2> $O/bench_c5ra_b4096.err || exit 3
-$T python bench.py --workload c5ra --batch 4096 --steps 10 --warmup 2 --streams 1 --no-cpu-baseline > $O/bench_c5ra_b4096_s1.json 2> $O/bench_c5ra_b4096_s1.err || exit 3
-$T rocprofv3 --kernel-trace --stats -d $O/prof512 -o run -- python bench.py --workload c5ra --batch 512 --steps 20 --warmup 2 --streams 1 --no-cpu-baseline > $O/prof512.log 2>&1 || exit 3
+$T python bench.py --full --workload c5ra --batch 512 --steps 40 --warmup 3 > $O/bench_c5ra_b512.json 2> $O/bench_c5ra_b512.err || exit 3
+$T python bench.py --full --workload c5ra --batch 512 --steps 40 --warmup 3 --streams 1 --no-cpu-baseline > $O/bench_c5ra_b512_s1.json 2> $O/bench_c5ra_b512_s1.err || exit 3
+$T python bench.py --full --workload c5ra --batch 4096 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c5ra_b4096.json 2> $O/bench_c5ra_b4096.err || exit 3
+$T python bench.py --full --workload c5ra --batch 4096 --steps 10 --warmup 2 --streams 1 --no-cpu-baseline > $O/bench_c5ra_b4096_s1.json 2> $O/bench_c5ra_b4096_s1.err || exit 3
+$T rocprofv3 --kernel-trace --stats -d $O/prof512 -o run -- python bench.py --full --workload c5ra --batch 512 --steps 20 --warmup 2 --streams 1 --no-cpu-baseline > $O/prof512.log 2>&1 || exit 3
 find $O/prof512 -name '*kernel_stats.csv' -exec cp {} $O/c5ra_b512_serial_kernel_stats.csv \;
 echo "c5ra 512 lines done"
 BATCH=512 STEPS=10 bash tools/c5_sweep.sh > $O/sweep512.log 2>&1 || { tail -5 $O/sweep512.log; exit 3; }

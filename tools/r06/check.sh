@@ -14,7 +14,7 @@ if [ $rc -gt 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { cat $O/smoke.txt; exit 3; }
 cat $O/smoke.txt
 for wl in ${WLS:-c2 c4 c4g}; do
-  timeout -k 10 240 python bench.py --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || { tail $O/bench_$wl.err; exit 3; }
+  timeout -k 10 240 python bench.py --full --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || { tail $O/bench_$wl.err; exit 3; }
   python -c "import json; d=json.load(open('$O/bench_$wl.json')); print('$wl', d['value']/1e9, d['ms_per_step'], d['decode_kernel_ms'], d['roofline']['frac'])"
 done
 exit $rc

@@ -16,7 +16,7 @@ for rep in 1 2; do
 for arm in prod rl8 rl16; do
 for wl in c4g c4; do
   if [ $arm = prod ]; then unset QLDPC_AB_BUILD; else export QLDPC_AB_BUILD=$arm; fi
-  timeout -k 10 300 python bench.py --workload $wl --steps 8 --warmup 2 --no-cpu-baseline > $O/${arm}_${wl}_$rep.json 2> $O/$wl.err || { tail -5 $O/$wl.err; exit 3; }
+  timeout -k 10 300 python bench.py --full --workload $wl --steps 8 --warmup 2 --no-cpu-baseline > $O/${arm}_${wl}_$rep.json 2> $O/$wl.err || { tail -5 $O/$wl.err; exit 3; }
   python3 -c "
 import json; d=json.load(open('$O/${arm}_${wl}_$rep.json'))
 print('$arm $wl', round(d['value']/1e9,4), 'Gbit/s decode', round(d['decode_kernel_ms'],2), 'step', round(d['ms_per_step'],2))"

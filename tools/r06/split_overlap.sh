@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest -q --timeout 300 --timeout-method thread -
 rc=$?; echo "pytest rc=$rc $(tail -1 $O/pytest.log)"; [ $rc -le 1 ] || exit $rc
 for rep in 1 2; do
 for wl in c4 c4g; do
-  timeout -k 10 300 python bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline > $O/${wl}_$rep.json 2> $O/$wl.err || { tail -5 $O/$wl.err; exit 3; }
+  timeout -k 10 300 python bench.py --full --workload $wl --steps 10 --warmup 2 --no-cpu-baseline > $O/${wl}_$rep.json 2> $O/$wl.err || { tail -5 $O/$wl.err; exit 3; }
   python3 -c "
 import json; d=json.load(open('$O/${wl}_$rep.json'))
 print('$wl', round(d['value']/1e9,4), 'Gbit/s decode', round(d['decode_kernel_ms'],2), 'step', round(d['ms_per_step'],2))"

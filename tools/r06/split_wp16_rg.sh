@@ -9,7 +9,7 @@ export QLDPC_DIAG=1
 O=gpurun_out/r06_wp16rg; mkdir -p $O
 run() {  # name, workload, env...
   local name=$1 wl=$2; shift 2
-  env "$@" timeout -k 10 300 python bench.py --workload $wl --steps 8 --warmup 2 --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; exit 3; }
+  env "$@" timeout -k 10 300 python bench.py --full --workload $wl --steps 8 --warmup 2 --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; exit 3; }
   python3 -c "
 import json; d=json.load(open('$O/$name.json'))
 print('$name', round(d['value']/1e9,4), 'Gbit/s decode', round(d['decode_kernel_ms'],2), 'step', round(d['ms_per_step'],2), d['config']['lanes_per_frame'], d['config']['edges_per_lane'])"
