@@ -40,8 +40,29 @@ $(CSRC)/trials.o: $(CSRC)/trials.hip $(CSRC)/decoder.hpp $(CSRC)/decoder_common.
 $(CSRC)/order.o: $(CSRC)/order.hip $(CSRC)/decoder.hpp $(CSRC)/decoder_common.hpp $(CSRC)/exact_math.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/capi.o: $(CSRC)/capi.hip $(CSRC)/decoder.hpp $(CSRC)/loaders.hpp $(CSRC)/relabel.hpp include/qkd_ldpc_hip.h
+# The library's host objects, named once for every link line ($(LIB), the stamp
+# build, the sanitizer build, `make ab`).  HOST_HIP are the host files that
+# include graph.hpp (and through it decoder.hpp): planners (plan.hip), index
+# tables (layout.hip), C ABI and launches (capi.hip), trial pipeline
+# (run_trials.hip).  host_algos.cpp, loaders.cpp and relabel.cpp see no HIP header.
+HOST_HIP := capi plan layout run_trials
+HOST_OBJS := $(HOST_HIP:=.o) host_algos.o loaders.o relabel.o
+GRAPH_HPP := $(CSRC)/graph.hpp $(CSRC)/decoder.hpp include/qkd_ldpc_hip.h
+
+$(CSRC)/capi.o: $(CSRC)/capi.hip $(GRAPH_HPP) $(CSRC)/loaders.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/plan.o: $(CSRC)/plan.hip $(GRAPH_HPP)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/layout.o: $(CSRC)/layout.hip $(GRAPH_HPP) $(CSRC)/relabel.hpp
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/run_trials.o: $(CSRC)/run_trials.hip $(GRAPH_HPP)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/host_algos.o: $(CSRC)/host_algos.cpp include/qkd_ldpc_hip.h
+	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 
 $(CSRC)/loaders.o: $(CSRC)/loaders.cpp $(CSRC)/loaders.hpp
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
@@ -49,19 +70,20 @@ $(CSRC)/loaders.o: $(CSRC)/loaders.cpp $(CSRC)/loaders.hpp
 $(CSRC)/relabel.o: $(CSRC)/relabel.cpp $(CSRC)/relabel.hpp
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 
-$(LIB): $(CSRC)/decoder.o $(CSRC)/decoder_v2.o $(CSRC)/trials.o $(CSRC)/order.o $(CSRC)/capi.o $(CSRC)/loaders.o $(CSRC)/relabel.o
+$(LIB): $(CSRC)/decoder.o $(CSRC)/decoder_v2.o $(CSRC)/trials.o $(CSRC)/order.o $(addprefix $(CSRC)/,$(HOST_OBJS))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -lz -o $@
 
-# Diagnostic build with per-phase s_memtime stamps (never the product).
+# Diagnostic build with per-phase s_memtime stamps (never the product).  On the
+# host side only capi.hip (decode_on) reads QL_PHASE_STAMPS.
 STAMPLIB := $(PKG)/diag/libqkdldpc_hip.so
 stamps: $(STAMPLIB)
 $(CSRC)/decoder_st.o: $(CSRC)/decoder.hip $(CSRC)/decoder_common.hpp $(CSRC)/decoder.hpp $(CSRC)/exact_math.h
 	$(HIPCC) $(HIPFLAGS) -DQL_PHASE_STAMPS -c $< -o $@
 $(CSRC)/decoder_v2_st.o: $(CSRC)/decoder_v2.hip $(CSRC)/decoder_common.hpp $(CSRC)/decoder.hpp $(CSRC)/exact_math.h
 	$(HIPCC) $(HIPFLAGS) $(V2FLAGS) -DQL_PHASE_STAMPS -c $< -o $@
-$(CSRC)/capi_st.o: $(CSRC)/capi.hip $(CSRC)/decoder.hpp $(CSRC)/loaders.hpp $(CSRC)/relabel.hpp include/qkd_ldpc_hip.h
+$(CSRC)/capi_st.o: $(CSRC)/capi.hip $(GRAPH_HPP) $(CSRC)/loaders.hpp
 	$(HIPCC) $(HIPFLAGS) -DQL_PHASE_STAMPS -c $< -o $@
-$(STAMPLIB): $(CSRC)/decoder_st.o $(CSRC)/decoder_v2_st.o $(CSRC)/trials.o $(CSRC)/order.o $(CSRC)/capi_st.o $(CSRC)/loaders.o $(CSRC)/relabel.o
+$(STAMPLIB): $(CSRC)/decoder_st.o $(CSRC)/decoder_v2_st.o $(CSRC)/trials.o $(CSRC)/order.o $(addprefix $(CSRC)/,$(patsubst capi.o,capi_st.o,$(HOST_OBJS)))
 	mkdir -p $(PKG)/diag
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -lz -o $@
 
@@ -101,7 +123,7 @@ clean:
 .PHONY: all clean stamps valu_bench
 
 # Sanitizer build: the host code of the product library (C ABI,
-# planner, relabelling, loaders, launch code), the CPU oracle and the two C++
+# planner, index tables, relabelling, loaders, launch code), the CPU oracle and the C++
 # drivers under ASan + UBSan (clang's runtime, the one hipcc links), into
 # build/asan/.  `make asan-check` runs the CPU test suite against it
 # (tools/asan_check.sh).  Device code is unchanged: GPU sanitizers are not
@@ -111,8 +133,8 @@ LLVM_BIN := /opt/rocm/lib/llvm/bin
 SANFLAGS := -fsanitize=address -fsanitize=undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g
 HIP_SAN := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined \
            -Xarch_host -fno-omit-frame-pointer -g
-ASAN_HIP_OBJS := $(ASAN)/decoder.o $(ASAN)/decoder_v2.o $(ASAN)/trials.o $(ASAN)/order.o $(ASAN)/capi.o
-$(ASAN)/%.o: $(CSRC)/%.hip $(CSRC)/decoder.hpp $(CSRC)/decoder_common.hpp $(CSRC)/exact_math.h $(CSRC)/relabel.hpp $(CSRC)/loaders.hpp include/qkd_ldpc_hip.h
+ASAN_DEV_OBJS := $(ASAN)/decoder.o $(ASAN)/decoder_v2.o $(ASAN)/trials.o $(ASAN)/order.o
+$(ASAN)/%.o: $(CSRC)/%.hip $(GRAPH_HPP) $(CSRC)/decoder_common.hpp $(CSRC)/exact_math.h $(CSRC)/relabel.hpp $(CSRC)/loaders.hpp
 	mkdir -p $(ASAN)
 	$(HIPCC) $(HIPFLAGS) $(HIP_SAN) -c $< -o $@
 $(ASAN)/loaders.o: $(CSRC)/loaders.cpp $(CSRC)/loaders.hpp
@@ -121,7 +143,10 @@ $(ASAN)/loaders.o: $(CSRC)/loaders.cpp $(CSRC)/loaders.hpp
 $(ASAN)/relabel.o: $(CSRC)/relabel.cpp $(CSRC)/relabel.hpp
 	mkdir -p $(ASAN)
 	$(LLVM_BIN)/clang++ -O1 -std=c++17 -fPIC -Wall $(SANFLAGS) -c $< -o $@
-$(ASAN)/libqkdldpc_hip.so: $(ASAN_HIP_OBJS) $(ASAN)/loaders.o $(ASAN)/relabel.o
+$(ASAN)/host_algos.o: $(CSRC)/host_algos.cpp include/qkd_ldpc_hip.h
+	mkdir -p $(ASAN)
+	$(LLVM_BIN)/clang++ -O1 -std=c++17 -fPIC -Wall $(SANFLAGS) -c $< -o $@
+$(ASAN)/libqkdldpc_hip.so: $(ASAN_DEV_OBJS) $(addprefix $(ASAN)/,$(HOST_OBJS))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -shared-libsan $(HIP_SAN) $^ -lz -o $@
 $(ASAN)/libqkdldpc_oracle.so: oracle/ldpc_oracle.c oracle/ldpc_oracle.h oracle/trials_oracle.cpp
 	mkdir -p $(ASAN)
@@ -142,12 +167,17 @@ asan-check: asan
 .PHONY: asan asan-check
 
 # A/B experiment build: `make ab AB=name AB_FLAGS=-D...` -> qkd_ldpc_v_amd/ab/name/
-# (AB_CAPI=1: capi.hip with the same flags too, for shapes the planner shares)
+# (AB_CAPI=1: the host files that include decoder.hpp, $(HOST_HIP), with the same
+# flags too, for shapes the planner shares: QL_SPLIT_R / QL_SPLIT_RG / QL_RL
+# change constants there, so all of them or none)
 # (selected at run time with QLDPC_DIAG=1 QLDPC_AB_BUILD=name; never the product)
 AB ?= x
+AB_DIR := $(PKG)/ab/$(AB)
 ab:
-	mkdir -p $(PKG)/ab/$(AB)
-	$(HIPCC) $(HIPFLAGS) $(V2FLAGS) $(AB_FLAGS) -c $(CSRC)/decoder_v2.hip -o $(PKG)/ab/$(AB)/decoder_v2.o
-	if [ -n "$(AB_CAPI)" ]; then $(HIPCC) $(HIPFLAGS) $(AB_FLAGS) -c $(CSRC)/capi.hip -o $(PKG)/ab/$(AB)/capi.o; else cp $(CSRC)/capi.o $(PKG)/ab/$(AB)/capi.o; fi
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(PKG)/ab/$(AB)/decoder_v2.o $(CSRC)/decoder.o $(CSRC)/trials.o $(CSRC)/order.o $(PKG)/ab/$(AB)/capi.o $(CSRC)/loaders.o $(CSRC)/relabel.o -lz -o $(PKG)/ab/$(AB)/libqkdldpc_hip.so
+	mkdir -p $(AB_DIR)
+	$(HIPCC) $(HIPFLAGS) $(V2FLAGS) $(AB_FLAGS) -c $(CSRC)/decoder_v2.hip -o $(AB_DIR)/decoder_v2.o
+	for f in $(HOST_HIP); do \
+	    if [ -n "$(AB_CAPI)" ]; then $(HIPCC) $(HIPFLAGS) $(AB_FLAGS) -c $(CSRC)/$$f.hip -o $(AB_DIR)/$$f.o || exit 1; \
+	    else cp $(CSRC)/$$f.o $(AB_DIR)/$$f.o || exit 1; fi; done
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(AB_DIR)/decoder_v2.o $(CSRC)/decoder.o $(CSRC)/trials.o $(CSRC)/order.o $(addprefix $(AB_DIR)/,$(HOST_HIP:=.o)) $(addprefix $(CSRC)/,$(filter-out $(HOST_HIP:=.o),$(HOST_OBJS))) -lz -o $(AB_DIR)/libqkdldpc_hip.so
 .PHONY: ab

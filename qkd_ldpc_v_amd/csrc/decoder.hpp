@@ -38,7 +38,7 @@ constexpr int V2_R_SPLIT = QL_SPLIT_R;
 // Split frames may add this many message slots per lane in per-workgroup
 // global scratch to the V2_R_SPLIT register/LDS slots (round 6): more edges
 // per part, so fewer parts per frame and more frames per XCD.  The planner
-// takes them only when they raise frames per XCD by >= 4/3 (capi.hip
+// takes them only when they raise frames per XCD by >= 4/3 (plan.hip
 // plan_v2_split).
 #ifndef QL_SPLIT_RG
 #define QL_SPLIT_RG 12
@@ -82,7 +82,7 @@ struct DecodeArgs {
     // decoder parameters
     int alg, max_it, thr_on;
     double thr, primary, secondary;
-    // SPA edge-form constants, computed by the host C library (capi.hip):
+    // SPA edge-form constants, computed by the host C library (capi.hip decode_on):
     double spa_tlim;  // tanh(min(thr, 44) / 2.)  (1 when clipping is off)
     double spa_ctop;  // 2. * atanh(1 - 2^-53)
     // frames
@@ -122,7 +122,7 @@ struct DecodeArgs {
     long long stage_wg_offset;      // doubles from a workgroup's scratch base to its stage
     const int32_t *row_orig;        // V2: layout row -> original row (syndrome index)
     // V2 scan (one workgroup per frame, register slots only): the row
-    // structure as lane masks and per-lane row slot masks (capi.hip)
+    // structure as lane masks and per-lane row slot masks (layout.hip build_meta)
     const uint64_t *row_sem;        // [waves][slots][4]: the lanes whose slot starts / ends a row / parks a tail
     const uint64_t *row_rmask;      // [nst_max][T]: slots of the lane's j-th started row; bit 63: open
     int nst_max;
@@ -209,7 +209,7 @@ hipError_t launch_decode(int variant, const DecodeArgs &a, int workgroups, size_
 // Max resident workgroups per CU for (variant, alg, T, lds).
 hipError_t occupancy(int variant, int alg, int T, size_t lds_bytes, int *blocks_per_cu);
 
-// The environment variable `name` under the diagnostic switch QLDPC_DIAG=1, else NULL (capi.hip):
+// The environment variable `name` under the diagnostic switch QLDPC_DIAG=1, else NULL (plan.hip):
 // the only way the library reads its QLDPC_* A/B knobs.
 const char *qldpc_diag_env(const char *name);
 constexpr size_t LDS_MAX_BYTES = 160 * 1024;

@@ -317,7 +317,7 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
     MetaSrcW<S> meta;
     meta.init(a.slot_meta, tid, T);
     // VN phase kk visits only the slots where some lane of this wave holds the
-    // kk-th edge of a bit (capi.hip: vn_mask[wave][kk]).
+    // kk-th edge of a bit (layout.hip: vn_mask[wave][kk]).
     const uint64_t *vn_mask = a.vn_mask + (size_t)wave * a.dv_max;
     // ... and per slot, the lanes whose edge there is a bit's kk-th: an exec
     // mask loaded by the scalar unit (no per-lane kpos test).
@@ -337,7 +337,7 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
     __amdgpu_buffer_rsrc_t meta2_rs = __builtin_amdgcn_make_buffer_rsrc(
         (void *)a.slot_meta2, (short)0, (GATHER || VNG) ? S / 4 * REG_TSTRIDE * 16 : 0, 0x00020000);
     const int k0 = GATHER ? a.vn_k0 : (VNG ? 1 : a.dv_max);
-    // Per-lane partition constants (capi.hip plan_v2): tail length, first row,
+    // Per-lane partition constants (plan.hip plan_v2, layout.hip build_meta): tail length, first row,
     // rows started here, and the wave's slot count (uniform across the wave).
     const int head_in0 = a.lane_head[tid];
     const int row0_in0 = a.lane_row0[tid];
@@ -1534,7 +1534,7 @@ bool v2_vng_ok(int alg, int R, int RG, int split_k, int dv_max, int m) {
 }
 
 // Every one-workgroup register shape gets row_sem from the planner only when
-// its slot count fits the 63 slot bits of a row mask (capi.hip build_meta):
+// its slot count fits the 63 slot bits of a row mask (layout.hip build_meta):
 // a larger shape would plan and then fail every launch below.
 static_assert(V2_R_TIGHT <= 63 && V2_R_SMALL <= 63 && V2_R_MID <= 63,
               "register shapes without RG slots must have <= 63 slots (row_sem / row_rmask)");

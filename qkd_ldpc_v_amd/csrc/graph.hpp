@@ -1,0 +1,307 @@
+// graph.hpp — what the host files of libqkdldpc_hip.so share: the graph and its
+// per-device state, the error helpers, the types that own device memory,
+// pinned memory, events, streams and the current device, and the few functions
+// that cross files (plan.hip, layout.hip, capi.hip, run_trials.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/qkd_ldpc_hip.h"
+#include "decoder.hpp"
+
+namespace qldpc {
+
+extern thread_local std::string g_last_error;  // capi.hip (qldpc_last_error)
+int fail(int code, const std::string &msg);
+int hip_fail(hipError_t e, const char *what);
+
+#define HIP_TRY(expr)                                         \
+    do {                                                      \
+        hipError_t _e = (expr);                               \
+        if (_e != hipSuccess) return hip_fail(_e, #expr);     \
+    } while (0)
+
+constexpr size_t LDS_LIMIT = 160 * 1024;
+
+// ---- owners (move-only) -------------------------------------------------------
+// Device memory (hipMalloc / hipFree) or, Pinned, host memory the copies stay
+// asynchronous with (hipHostMalloc / hipHostFree).
+template <typename T, bool Pinned>
+class GpuBuf {
+    T *p_ = nullptr;
+    static hipError_t release(T *p) { return Pinned ? hipHostFree(p) : hipFree(p); }
+
+public:
+    GpuBuf() = default;
+    GpuBuf(const GpuBuf &) = delete;
+    GpuBuf &operator=(const GpuBuf &) = delete;
+    GpuBuf(GpuBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    GpuBuf &operator=(GpuBuf &&o) noexcept {
+        std::swap(p_, o.p_);
+        return *this;
+    }
+    ~GpuBuf() {
+        if (p_) (void)release(p_);
+    }
+    T *get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    // Free, then allocate max(count, 1) elements.  (The caller synchronises
+    // first when the old buffer may still be in use.)
+    int alloc(size_t count) {
+        if (p_) HIP_TRY(release(p_));
+        p_ = nullptr;
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        if (Pinned) HIP_TRY(hipHostMalloc(&p_, bytes));
+        else HIP_TRY(hipMalloc(&p_, bytes));
+        return QLDPC_OK;
+    }
+    int upload(const std::vector<T> &src) {
+        static_assert(!Pinned, "upload is for device buffers");
+        if (int rc = alloc(src.size())) return rc;
+        if (!src.empty()) HIP_TRY(hipMemcpy(p_, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+        return QLDPC_OK;
+    }
+};
+template <typename T>
+using DevBuf = GpuBuf<T, false>;
+template <typename T>
+using PinnedBuf = GpuBuf<T, true>;
+
+// An event or stream its holder created (`if (!h) HIP_TRY(hipEventCreate(h.put()))`).
+template <typename H, hipError_t (*Destroy)(H)>
+class Owned {
+    H h_ = nullptr;
+
+public:
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    Owned(Owned &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Owned &operator=(Owned &&o) noexcept {
+        std::swap(h_, o.h_);
+        return *this;
+    }
+    ~Owned() {
+        if (h_) (void)Destroy(h_);
+    }
+    H get() const { return h_; }
+    operator H() const { return h_; }
+    H *put() { return &h_; }
+};
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+
+// The caller's current device, restored when the scope ends.
+class DeviceScope {
+    int prev_ = -1;
+
+public:
+    DeviceScope() = default;
+    DeviceScope(const DeviceScope &) = delete;
+    DeviceScope &operator=(const DeviceScope &) = delete;
+    ~DeviceScope() {
+        if (prev_ >= 0) (void)hipSetDevice(prev_);
+    }
+    int save() {  // (the devices are then selected by the work itself)
+        int d = 0;
+        HIP_TRY(hipGetDevice(&d));
+        prev_ = d;
+        return QLDPC_OK;
+    }
+    int enter(int device) {
+        if (int rc = save()) return rc;
+        HIP_TRY(hipSetDevice(device));
+        return QLDPC_OK;
+    }
+};
+
+// ---- per-device state ---------------------------------------------------------
+struct Workspace {  // per (device, stream): frame counter + decoder scratch
+    DevBuf<int> counter;
+    DevBuf<double> scratch;
+    size_t scratch_doubles = 0;
+    // V2 frame format (palette + 2-bit codes), capacity in frames
+    DevBuf<uint8_t> codes, pal_ok;
+    DevBuf<double> palette;
+    size_t code_frames = 0;
+    // V2 split frames: group claim / publish / barrier / mismatch slots and the
+    // frames' totals, capacity in frames
+    DevBuf<int> split_ctl;
+    DevBuf<double> gtotal, gstage;
+    size_t split_frames = 0;
+    // frame claim order (order.hip): per-frame weights and the sorted order
+    DevBuf<int32_t> fweight, forder;
+    size_t order_frames = 0;
+    int order_count = 0;  // frames of the last decode claimed through forder (0: index order)
+    // the fused entries' frame LLRs when the caller passes no workspace and the
+    // graph's decoder reads llr[] (not V2), capacity in frames
+    DevBuf<double> llr_ws;
+    size_t llr_ws_frames = 0;
+    // kernel timing (qldpc_set_kernel_timing): events around the last decode launch
+    Event ev0, ev1;
+    bool ev_recorded = false;
+};
+
+struct HostIO {  // device staging buffers of the host-buffer entry
+    DevBuf<double> llr, post;
+    DevBuf<uint8_t> synd, bits, ok;
+    DevBuf<uint32_t> iters;
+    size_t cap_frames = 0;
+    Stream stream;
+};
+
+// qldpc_run_trials: one pipeline slot of a device's trial batches — the
+// chunk's seeds, keys and results on device, its results in pinned host memory
+// (two slots per device: chunk c + 1's trials are generated while chunk c
+// decodes on the other stream).
+struct TrialSlot {
+    Stream stream;
+    // the chunk's window: from ev0 (after its trials are generated) or the end
+    // of the other slot's chunk before it (prev_end), whichever is later, to
+    // ev1 (after the key compare).  ev1 alternates over ev_end, so the other
+    // slot's next chunk never re-records the end a window is measured from.
+    // (ev1 and prev_end alias an ev_end of this or the other slot: not owned.)
+    Event ev0, ev_end[2];
+    hipEvent_t ev1 = nullptr, prev_end = nullptr;
+    int ev_i = 0;
+    DevBuf<uint64_t> seeds, clk;
+    DevBuf<uint8_t> alice, bob, palice, pbob, alice_ext;
+    DevBuf<uint8_t> synd, bits, ok, km;
+    DevBuf<uint32_t> iters, tscratch;
+    DevBuf<double> logp;
+    PinnedBuf<uint32_t> h_iters;
+    PinnedBuf<uint8_t> h_ok, h_km;
+    PinnedBuf<uint64_t> h_clk, h_seeds;  // pinned: the copies stay asynchronous
+    PinnedBuf<double> h_logp;
+    size_t cap = 0, cap_punct = 0, tscratch_words = 0;
+    int f0 = 0, nb = 0;  // the chunk in flight (nb == 0: none)
+    qldpc_trials_job *owner = nullptr;  // the job whose results it holds
+};
+
+struct DeviceGraph {
+    int device = 0;
+    int num_cus = 0;
+    DevBuf<uint32_t> slot_meta;
+    DevBuf<int32_t> lane_row0, lane_head, ell_col, row_deg;
+    DevBuf<int32_t> wave_rows;
+    DevBuf<int32_t> lane_nst, lane_epl;
+    DevBuf<uint32_t> slot_meta_ms;                  // V2 min-sum: rows listed by kpos
+    DevBuf<uint64_t> vn_mask, vn_mask_ms;           // V2: [wave][dv_max] slot masks
+    DevBuf<uint64_t> vn_exec, vn_exec_ms;           // V2: [wave][dv_max][slot] lane masks
+    DevBuf<uint32_t> slot_meta2, slot_meta2_ms;     // V2 hybrid: stage index per slot
+    DevBuf<int32_t> hd_bits, hd_dv, stage_off;
+    DevBuf<int32_t> row_orig;   // V2: layout row -> original row (syndrome index)
+    DevBuf<int32_t> part_row0;  // V2 split: first layout row of each part
+    DevBuf<int32_t> xoff;       // V2 split exchange: region starts
+    DevBuf<uint16_t> xbit, xbit_ms;  // ... chunk-local bit per stage position (CSR / kpos layouts)
+    DevBuf<int32_t> iso_bits;
+    DevBuf<uint32_t> vn_rows;  // V2 min-sum bit gather: [n or chunks][2] four u16 layout rows
+    DevBuf<uint32_t> vng_bits, vng_meta2;  // hybrid bit gather: bit order, slot positions
+    DevBuf<uint32_t> vng_rec;  // register-shape bit gather: per slot, the code word's byte offset | shift << 16
+    DevBuf<uint64_t> row_sem;    // V2 scan: [wave][slot][4] START / END / PARK lane masks (+ pad)
+    DevBuf<uint64_t> row_rmask;  // V2 scan: [row j][lane] slots of the lane's j-th started row
+    DevBuf<int32_t> col_orig, col_lab;  // V2 bank relabelling: label -> bit id, bit id -> label
+    DevBuf<int32_t> ell_lab;     // row-ELL in labels (the claim order reads label-ordered frame codes)
+    DevBuf<int32_t> pair_src, pair_col;  // v1 occurrence pairing (unsorted adjacency), [k][lane]
+    std::mutex mu;     // workspaces (ws), occupancy cache
+    std::map<void *, Workspace> ws;
+    std::mutex io_mu;  // the host-buffer entry's staging buffers and stream, held copy-in .. copy-out
+    HostIO io;
+    std::mutex trial_mu;  // qldpc_run_trials' pipeline slots: held while a job enqueues or harvests
+    TrialSlot tslot[2];
+    int next_slot = 0;    // the slot the next chunk takes (the two alternate)
+    int occ[6] = {0, 0, 0, 0, 0, 0};
+    DeviceGraph() = default;
+    // Its device is selected (the caller restores its own) and idle before the
+    // members release what they own.
+    ~DeviceGraph() {
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+    }
+};
+
+// The index tables of one graph on the host (layout.hip fills them, capi.hip
+// uploads them to each device; the fields carry DeviceGraph's / DecodeArgs'
+// names).  layout_digest hashes them in this order.
+struct GraphTables {
+    std::vector<uint32_t> slot_meta, slot_meta_ms;
+    std::vector<uint64_t> vn_mask, vn_mask_ms, vn_exec, vn_exec_ms;
+    std::vector<uint32_t> slot_meta2, slot_meta2_ms;
+    std::vector<int32_t> hd_bits, hd_dv, stage_off, row_orig, part_row0, xoff;
+    std::vector<uint16_t> xbit, xbit_ms;
+    std::vector<int32_t> lane_row0, wave_rows, lane_head, lane_nst, lane_epl, ell_col, row_deg, iso_bits;
+    std::vector<uint32_t> vn_rows, vng_bits, vng_meta2;
+    std::vector<uint64_t> row_sem;
+    std::vector<uint32_t> vng_rec;
+    std::vector<uint64_t> row_rmask;
+    std::vector<int32_t> pair_src, pair_col, col_orig, col_lab, ell_lab;
+};
+
+}  // namespace qldpc
+
+// Rate-adaptation plan: per position its class (0 key, 1 punctured, 2
+// shortened) and source index, replicated on the graph's devices.
+struct qldpc_rate_plan {
+    struct Dev {
+        int device;
+        qldpc::DevBuf<uint8_t> cls;
+        qldpc::DevBuf<int32_t> src;
+    };
+    int n_punct = 0, n_short = 0;
+    std::vector<Dev> devs;
+};
+
+struct qldpc_graph {
+    int n = 0, m = 0, E = 0, T = 0, EPL = 0, dv_max = 0, max_dc = 0, variant = 0;
+    bool vng = false;                       // V2 min-sum bit gather tables built
+    bool vng_h_fit = false;                 // hybrid bit gather's padded edge codes fit LDS (set before planning)
+    bool rows_global_ms = false;            // hybrid min-sum: row aggregates (partly) in global scratch
+    int rows_lds_ms = 0, rows_lds_waves_ms = 0;  // ... of which the rows of the first waves stay in LDS
+    int v2R = 0, v2RG = 0, n_iso = 0;       // V2: register / scratch slots per lane, bits of degree 0
+    std::vector<int> wave_rows;             // V2: first layout row of each wave (+ m)
+    std::vector<int> row_order;             // V2: layout row -> original row
+    std::vector<int> layout_row_ptr;        // V2: row_ptr of the rows in layout order
+    int vn_k0 = 0, n_hd = 0;                // V2 hybrid: first staged VN term, bits of degree > vn_k0
+    bool paired = false;                    // unsorted adjacency: v1 global-slot kernel with occurrence pairing
+    int hd_uniform_dv = 0;                  // > 0: the staged bits are 0..n-1 in order, all of this degree
+    int nst_max = 0;                        // V2 SPA scan: most rows started in one lane (row_rmask rows)
+    long long stage_doubles = 0;            // V2 hybrid: staged VN terms per frame
+    int split_k = 1, split_mrows = 0;       // V2 split: workgroups per frame, rows of the largest part
+    int split_cb = 0, split_nc = 0;         // V2 split exchange gather: bits per LDS chunk, chunks per part (0: off)
+    int split_pl = qldpc::REG_TSTRIDE;      // V2 split: a part's lanes (1024: 16 waves; 512: 8 waves, 2 per CU)
+    bool kernel_timing = false;             // qldpc_set_kernel_timing
+    std::vector<int32_t> col_lab;           // V2 bank relabelling (relabel.cpp): bit id -> label; empty: identity
+    long long relabel_stats[4] = {0, 0, 0, 0};  // bank excess before / after, busiest-bank cycles before / after
+    std::vector<int> part_row0;             // V2 split: first layout row of each part (+ m)
+    std::vector<std::unique_ptr<qldpc::DeviceGraph>> devs;
+};
+
+namespace qldpc {
+
+// plan.hip — (variant, T, EPL) and the V2 row deal of a classified graph
+int env_int(const char *name, int dflt);  // a QLDPC_* knob under the diagnostic switch
+void plan(qldpc_graph &g);
+bool plan_v2(qldpc_graph &g, const int32_t *row_ptr);
+bool plan_v2_split(qldpc_graph &g, const int32_t *row_ptr, const int32_t *col_idx);
+
+// layout.hip — validate, plan, build every table; touches no device
+int build_layout(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
+                 const int32_t *row_idx, std::unique_ptr<qldpc_graph> &out, GraphTables &t);
+
+// capi.hip — used by run_trials.hip
+int check_params(const qldpc_params *p);
+int split_check(qldpc_graph *g, DeviceGraph *dg, hipStream_t stream);
+int qkd_ldpc_window(qldpc_graph *g, DeviceGraph *dg, const qldpc_rate_plan *plan, const qldpc_params *p, int batch,
+                    const uint8_t *d_alice, const uint8_t *d_bob, const uint8_t *d_punct_alice,
+                    const uint8_t *d_punct_bob, const double *d_log_p, uint8_t *d_alice_ext, double *d_llr_ws,
+                    uint8_t *d_synd_ws, uint8_t *d_bits_out, uint32_t *d_iters_out, uint8_t *d_synd_ok_out,
+                    uint8_t *d_keys_match_out, hipStream_t s, uint64_t *frame_clk = nullptr,
+                    hipEvent_t before_decode = nullptr);
+
+}  // namespace qldpc

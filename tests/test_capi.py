@@ -139,7 +139,7 @@ def test_split_part_size_by_frames_per_xcd():
     assert Q.Graph(load_fixture("c2_n10240_m2201.alist"), host_only=True).split_plan()["parts"] == 1
 
 
-# Every QLDPC_* A/B knob the library or its loader reads (capi.hip env_int /
+# Every QLDPC_* A/B knob the library or its loader reads (plan.hip env_int /
 # qldpc_diag_env, trials.hip, _lib.py); none may act without QLDPC_DIAG=1.
 TUNING_KNOBS = {
     "QLDPC_VARIANT": "v1", "QLDPC_V2_WAVES": "12", "QLDPC_ROWS_LDS": "0", "QLDPC_RGLB_SHARE": "40",
@@ -204,7 +204,7 @@ def test_loader_ignores_build_selectors_without_diag_switch():
 
 def test_library_reads_environment_only_through_the_diag_gate():
     """Static check of the product sources: the only getenv calls are the
-    diagnostic gate itself (capi.hip qldpc_diag_env) — every knob goes through
+    diagnostic gate itself (plan.hip qldpc_diag_env) — every knob goes through
     it — and the drop-in's device selection (QKD_LDPC_HIP_DEVICES, not a
     tuning knob: which GPUs the reference's driver runs on)."""
     import glob

@@ -311,7 +311,7 @@ def test_c4_100k_all_global_variant(gpu_available, alg, prim, sec):
     assert graph("c4s_n102400_m32001.alist", "v1").plan(0, alg)["variant"] == "glb_glb"
 
 
-# n = 100k: a frame is split over several workgroups of one XCD (capi.hip plan_v2_split)
+# n = 100k: a frame is split over several workgroups of one XCD (plan.hip plan_v2_split)
 @pytest.mark.parametrize("alg,prim,sec", ALGS)
 def test_c4_100k_split_variant(gpu_available, alg, prim, sec):
     assert_parity("c4s_n102400_m32001.alist", alg, prim, sec, qber=0.038, batch=10, max_it=8, seed=40 + alg)
@@ -715,3 +715,49 @@ def test_frame_claim_order(gpu_available, monkeypatch, name, alg, prim, sec, qbe
     for x, y in zip(r1[:3], r0[:3]):
         assert np.array_equal(x, y)
     assert bits_equal_nan(r1[3], r0[3])
+
+
+def _device_entry_parity(g, H, O, alg, prim, sec, qber, batch, max_it, seed):
+    """One batch through qldpc_decode_batch_device on the current stream: bits,
+    iterations, syndromes_match and posteriors bitwise equal to the oracle."""
+    import torch
+
+    _, _, llr, synd = frames(H, qber, batch, seed)
+    dev = torch.device("cuda:0")
+    tl = torch.from_numpy(np.ascontiguousarray(llr)).to(dev)
+    ts = torch.from_numpy(np.ascontiguousarray(synd)).to(dev)
+    bits = torch.empty((batch, H.n), dtype=torch.uint8, device=dev)
+    it = torch.empty(batch, dtype=torch.int32, device=dev)
+    ok = torch.empty(batch, dtype=torch.uint8, device=dev)
+    post = torch.empty((batch, H.n), dtype=torch.float64, device=dev)
+    g.decode_device(Q.Params(alg, max_it, True, 100.0, prim, sec), tl, ts, bits, it, ok, post)
+    torch.cuda.synchronize()
+    ob, oi, ook, op = O.decode_batch(O.params(alg, max_it, True, 100.0, prim, sec), llr, synd, threads=16,
+                                     posterior=True)
+    what = (alg, batch)
+    assert np.array_equal(bits.cpu().numpy(), ob), what
+    assert np.array_equal(it.cpu().numpy().astype(np.uint32), oi), what
+    assert np.array_equal(ok.cpu().numpy(), ook), what
+    assert bits_equal_nan(post.cpu().numpy(), op), what
+
+
+def test_workspace_regrows_between_batches_c1(gpu_available):
+    """A fresh graph's stream workspace (frame codes, claim order, scratch)
+    grows from 4 to 96 frames and is reused for 4 again, SPA and OMSA."""
+    H = load_fixture("c1_n1024_m220.alist")
+    g, O = Q.Graph(H), Oracle(H)
+    for alg, prim in ((Q.SPA, 0.0), (Q.OMSA, 0.77)):
+        for i, batch in enumerate((4, 96, 4)):
+            _device_entry_parity(g, H, O, alg, prim, 0.0, 0.03, batch, 50, seed=900 + 10 * alg + i)
+    g.close()
+
+
+def test_workspace_regrows_between_batches_c4_split(gpu_available):
+    """Split frames: the group control slots, totals and stage of the stream
+    workspace (split_ctl / gtotal / gstage) grow from 1 to 3 frames, then 1."""
+    H = load_fixture("c4s_n102400_m32001.alist")
+    g, O = Q.Graph(H), Oracle(H)
+    assert g.plan(0, Q.SPA)["variant"] == "v2_split"
+    for i, batch in enumerate((1, 3, 1)):
+        _device_entry_parity(g, H, O, Q.SPA, 0.0, 0.0, 0.038, batch, 3, seed=950 + i)
+    g.close()
