@@ -438,7 +438,10 @@ struct Layout {
         std::vector<std::vector<uint64_t>> rm(rowstruct ? T : 0);
         if (rowstruct) row_sem.assign((size_t)W * S4 * 4, 0);
         mt.assign((size_t)G4 * TS * 4 * NPARTS, 0);
-        mt2.assign(g->n_hd ? (size_t)G4 * TS * 4 * NPARTS : 0, 0);
+        // (the hybrid shape's SPA message pass loads a slot_meta2 word beside every
+        // slot_meta word, staged terms or not: with dv_max <= 4 there is no stage
+        // and the words stay 0, but the table must span the slots)
+        mt2.assign((g->n_hd || (v2 && g->v2RG > 0)) ? (size_t)G4 * TS * 4 * NPARTS : 0, 0);
         vnm.assign(v2 ? (size_t)W * g->dv_max : 0, 0);
         vex.assign(v2 ? (size_t)W * g->dv_max * S4 : 0, 0);
         perm = ledge;
@@ -462,7 +465,6 @@ struct Layout {
                     lrow0[l] = r0;
                     if (e0 != lrp[r0]) head = lhead[l] = lrp[r0 + 1] - (int)e0;
                 }
-                int prev_row = -1;
                 for (int k = 0; k < (v2 ? G4 * 4 : epl_w); ++k) {
                     const long long e = e0 + k;  // position in the row-major edge list
                     uint32_t wd;
@@ -506,9 +508,6 @@ struct Layout {
                             wd |= META_END;
                             if (rowstruct) row_sem[((size_t)w * S4 + k) * 4 + 1] |= 1ull << li;
                         }
-                        if (k > 0 && j != prev_row && j != prev_row + 1)
-                            return fail(QLDPC_EUNSUP, "empty check rows between non-empty rows are not supported");
-                        prev_row = j;
                     }
                     mt[midx(l, k)] = wd;
                     // min-sum: a lane's tail aggregate (a row begun in the lane
@@ -713,6 +712,17 @@ int build_layout(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *co
         if (row_ptr[j + 1] < row_ptr[j]) return fail(QLDPC_EINVAL, "row_ptr must be non-decreasing");
     const int E = row_ptr[m];
     if (E <= 0) return fail(QLDPC_EINVAL, "graph has no edges");
+    // Empty check rows: before the first and after the last non-empty row only
+    // (v1 decodes those; a lane's row counter steps by one per row start, so
+    // an empty row between two others is refused wherever it falls).
+    {
+        int first = 0, last = m - 1;
+        while (row_ptr[first + 1] == row_ptr[first]) ++first;
+        while (row_ptr[last + 1] == row_ptr[last]) --last;
+        for (int j = first; j <= last; ++j)
+            if (row_ptr[j + 1] == row_ptr[j])
+                return fail(QLDPC_EUNSUP, "empty check rows between non-empty rows are not supported");
+    }
 
     auto g = std::make_unique<qldpc_graph>();
     g->n = n;

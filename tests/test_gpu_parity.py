@@ -243,7 +243,9 @@ def _irregular_dv4_code(n=4096, m=900, seed=5):
         d = int(rng.choice([0, 1, 2, 3, 4], p=[0.02, 0.08, 0.3, 0.3, 0.3]))
         for r in rng.choice(m, size=d, replace=False):
             rows[int(r)].add(b)
-    for r in range(m):  # every row at least 2 edges (a 1-edge row keeps min2 = DBL_MAX)
+    # every row at least 2 edges here; 1-edge rows (min2 stays DBL_MAX, SPA posteriors turn NaN
+    # with the threshold off) are tests/test_gpu_shapes.py::test_degree1_rows
+    for r in range(m):
         while len(rows[r]) < 2:
             rows[r].add(int(rng.integers(n)))
     return Q.HMatrix.from_check_nodes(n, [sorted(r) for r in rows])
