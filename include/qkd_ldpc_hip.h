@@ -118,6 +118,55 @@ int qldpc_graph_create_checked_on(int32_t n, int32_t m, const int32_t *row_ptr, 
 int qldpc_graph_create_host(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *col_idx,
                             qldpc_graph **out);
 
+/* Graph creation with options: every entry above through one door, plus the
+ * choice of layout.
+ *
+ * layout QLDPC_LAYOUT_AUTO (or opts == NULL) is the planner's choice, the
+ * same graph (plan, labels, tables) as qldpc_graph_create_checked_on builds;
+ * col_ptr / row_idx NULL takes bit_nodes as the ascending transpose
+ * (qldpc_graph_create_on), host_only != 0 plans without touching a device
+ * (qldpc_graph_create_host; devices is ignored).  devices NULL: the current
+ * device.
+ *
+ * QLDPC_LAYOUT_FRAME_PER_LANE ("fpl") decodes 64 frames per wave, lane =
+ * frame: the batch is cut into tiles of 64 frames, and every iteration is a
+ * short sequence of ordinary kernel launches on the caller's stream (a
+ * check-node pass of one wave per row, a settle step, a bit pass).  No kernel
+ * of it waits on another workgroup, so unlike the split plan of n = 100k
+ * codes it cannot fail to meet: choose it under co-tenancy, CU masks,
+ * several ranks on one device or a large max_iterations.  It takes any graph
+ * the canonical adjacency allows and any batch size; bit_nodes that need the
+ * reference's occurrence pairing return QLDPC_EUNSUP (those graphs stay on
+ * the first-generation kernels).  Every decode entry works on it unchanged:
+ *   - the launch count is a fixed function of max_iterations and the graph's
+ *     row lengths: per iteration one check-node launch per class of row
+ *     lengths present (at most 8; 1-3 for the shipped codes), a settle and a
+ *     bit-pass launch, plus six launches per chunk; the device entries enqueue the whole sequence,
+ *     frames that have exited are masked and finished tiles return at once;
+ *   - device memory per tile of 64 frames is 512 nnz + 1024 n + 8 (n + m)
+ *     bytes in the (device, stream) workspace; a batch whose tiles exceed a
+ *     budget of 4 GiB runs as consecutive chunks of tiles on the same stream;
+ *   - the fused entries use the internal LLR workspace when d_llr_ws is NULL;
+ *   - qldpc_graph_plan answers variant "fpl", lanes 64, edges_per_lane 0,
+ *     lds_bytes 0 and for workgroups the check-node pass's grid for one
+ *     tile; qldpc_graph_split_plan parts 1, part_lanes 64, scratch_slots 0;
+ *     qldpc_graph_labels the identity;
+ *   - qldpc_set_kernel_timing brackets the whole launch sequence of a decode;
+ *     qldpc_last_claim_order reports the order in which frames were dealt to
+ *     tiles (64 consecutive entries share a tile; count 0: index order).
+ * An unknown layout or a nonzero reserved word returns QLDPC_EINVAL. */
+#define QLDPC_LAYOUT_AUTO 0
+#define QLDPC_LAYOUT_FRAME_PER_LANE 1
+typedef struct {
+    int32_t layout;
+    int32_t host_only;
+    int32_t reserved[6];
+} qldpc_graph_opts;
+int qldpc_graph_create_opts(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *col_idx,
+                            const int32_t *col_ptr /* nullable */, const int32_t *row_idx /* nullable */,
+                            const int32_t *devices /* nullable: current device */, int32_t ndevices,
+                            const qldpc_graph_opts *opts /* NULL = all zero */, qldpc_graph **out);
+
 void qldpc_graph_destroy(qldpc_graph *g);
 
 /* n, m, nnz and the number of devices the graph lives on. */

@@ -55,6 +55,13 @@ class qldpc_params(ctypes.Structure):
     ]
 
 
+class qldpc_graph_opts(ctypes.Structure):
+    _fields_ = [("layout", ctypes.c_int32), ("host_only", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+LAYOUT_AUTO, LAYOUT_FRAME_PER_LANE = 0, 1
+LAYOUTS = {"auto": LAYOUT_AUTO, "frame_per_lane": LAYOUT_FRAME_PER_LANE}
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _PI32 = ctypes.POINTER(ctypes.c_int32)
@@ -67,6 +74,8 @@ _SIGNATURES = {
     "qldpc_graph_create_on": (_I32, [_I32, _I32, _P, _P, _P, _I32, ctypes.POINTER(_P)]),
     "qldpc_graph_create_checked_on": (_I32, [_I32, _I32, _P, _P, _P, _P, _P, _I32, ctypes.POINTER(_P)]),
     "qldpc_graph_create_host": (_I32, [_I32, _I32, _P, _P, ctypes.POINTER(_P)]),
+    "qldpc_graph_create_opts": (_I32, [_I32, _I32, _P, _P, _P, _P, _P, _I32, ctypes.POINTER(qldpc_graph_opts),
+                                       ctypes.POINTER(_P)]),
     "qldpc_graph_labels": (_I32, [_P, _P, _P]),
     "qldpc_graph_destroy": (None, [_P]),
     "qldpc_set_kernel_timing": (_I32, [_P, _I32]),

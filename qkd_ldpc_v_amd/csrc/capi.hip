@@ -47,6 +47,7 @@ const char *variant_name(int v) {
     case VAR_REG_LDS: return "reg_lds";
     case VAR_GLB_LDS: return "glb_lds";
     case VAR_V2: return "v2";
+    case VAR_FPL: return "fpl";
     default: return "glb_glb";
     }
 }
@@ -57,6 +58,7 @@ int block_threads(const qldpc_graph &g) {
 }
 
 size_t lds_of(const qldpc_graph &g, int alg) {
+    if (g.variant == VAR_FPL) return 0;  // (its transposes' LDS is static)
     if (g.variant == VAR_V2 && g.split_k > 1)
         return lds_bytes_v2(alg, g.n, g.split_mrows, g.split_pl, true, 0, 0, -1, g.split_cb);
     return g.variant == VAR_V2 ? lds_bytes_v2(alg, g.n, g.m, g.T, false, g.v2R, g.v2RG,
@@ -84,6 +86,10 @@ int upload_tables(DeviceGraph &dg, const qldpc_graph &g, const GraphTables &t) {
         (rc = dg.vng_meta2.upload(t.vng_meta2)) || (rc = dg.row_sem.upload(t.row_sem)) ||
         (rc = dg.vng_rec.upload(t.vng_rec)) ||
         (rc = dg.row_rmask.upload(t.row_rmask)) ||
+        (g.variant == VAR_FPL &&
+         ((rc = dg.fpl_row_ptr.upload(t.fpl_row_ptr)) || (rc = dg.fpl_col.upload(t.fpl_col)) ||
+          (rc = dg.fpl_cslot.upload(t.fpl_cslot)) || (rc = dg.fpl_col_ptr.upload(t.fpl_col_ptr)) ||
+          (rc = dg.fpl_rows.upload(t.fpl_rows)))) ||
         (g.paired && ((rc = dg.pair_src.upload(t.pair_src)) || (rc = dg.pair_col.upload(t.pair_col)))) ||
         (!t.col_orig.empty() && ((rc = dg.col_orig.upload(t.col_orig)) || (rc = dg.col_lab.upload(t.col_lab)) ||
                                  (rc = dg.ell_lab.upload(t.ell_lab)))))
@@ -97,13 +103,13 @@ int upload_tables(DeviceGraph &dg, const qldpc_graph &g, const GraphTables &t) {
 // own order): NULL means the ascending transpose of check_nodes.
 int build_graph(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *col_idx, int32_t device_mask,
                 qldpc_graph **out, bool host_only = false, const std::vector<int> *device_list = nullptr,
-                const int32_t *col_ptr = nullptr, const int32_t *row_idx = nullptr) {
+                const int32_t *col_ptr = nullptr, const int32_t *row_idx = nullptr, int layout = QLDPC_LAYOUT_AUTO) {
     if (!out) return fail(QLDPC_EINVAL, "out is NULL");
     *out = nullptr;
     DeviceScope restore;  // (outlives g: a graph dropped on an error selects its devices as it goes)
     std::unique_ptr<qldpc_graph> g;
     GraphTables t;
-    if (int rc = build_layout(n, m, row_ptr, col_idx, col_ptr, row_idx, g, t)) return rc;
+    if (int rc = build_layout(n, m, row_ptr, col_idx, col_ptr, row_idx, g, t, layout)) return rc;
     if (host_only) {
         *out = g.release();
         return QLDPC_OK;
@@ -271,6 +277,95 @@ int qldpc::split_check(qldpc_graph *g, DeviceGraph *dg, hipStream_t stream) {
 
 namespace {
 
+// Frame-per-lane workspace budget per (device, stream): a batch whose tiles
+// need more runs as consecutive chunks of tiles on the same stream.  4 GiB
+// holds 13-16 tiles (832-1024 frames) of the n = 102,400 codes.
+constexpr size_t FPL_BUDGET_BYTES = (size_t)4 << 30;
+
+// decode_on for a frame-per-lane graph: deal the frames to tiles of 64, then
+// enqueue every chunk's launch sequence (decoder_fpl.hip).  Nothing is read
+// back: the sequence's length depends on max_iterations and the graph alone.
+int decode_fpl_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch, const double *llr,
+                  const uint8_t *synd, uint8_t *bits, uint32_t *iters, uint8_t *ok, double *post, hipStream_t stream,
+                  uint64_t *frame_clk, hipEvent_t before_decode) {
+    const size_t tile_words = fpl_tile_words(g->n, g->m, g->E);
+    const int tiles_all = (batch + FPL_LANES - 1) / FPL_LANES;
+    int chunk = (int)std::min<size_t>((size_t)tiles_all, std::max<size_t>(1, FPL_BUDGET_BYTES / (tile_words * 8)));
+    {  // QLDPC_FPL_TILES=k (diagnostic switch): k tiles per chunk
+        const int k = env_int("QLDPC_FPL_TILES", 0);
+        if (k > 0) chunk = std::min(k, tiles_all);
+    }
+    chunk = std::min(chunk, 65535);  // (tiles are the grids' y dimension)
+    Workspace *w;
+    {
+        std::lock_guard<std::mutex> lk(dg->mu);
+        w = workspace(dg, stream);
+        int rc;
+        if ((size_t)chunk > w->fpl_tiles) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            w->fpl_tiles = 0;
+            if ((rc = w->fpl.alloc((size_t)chunk * tile_words))) return rc;
+            w->fpl_tiles = (size_t)chunk;
+        }
+        if ((size_t)batch > w->order_frames) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            w->order_frames = 0;
+            if ((rc = w->fweight.alloc((size_t)batch)) || (rc = w->forder.alloc((size_t)batch))) return rc;
+            w->order_frames = (size_t)batch;
+        }
+    }
+    FplArgs a{};
+    a.n = g->n; a.m = g->m; a.E = g->E;
+    a.row_ptr = dg->fpl_row_ptr.get(); a.col_idx = dg->fpl_col.get();
+    a.rows = dg->fpl_rows.get();
+    for (int c = 0; c <= FPL_CLASSES; ++c) a.class_off[c] = g->fpl_class_off[c];
+    a.cslot = dg->fpl_cslot.get(); a.col_ptr = dg->fpl_col_ptr.get();
+    a.alg = p->algorithm; a.max_it = p->max_iterations; a.thr_on = p->thr_enabled ? 1 : 0;
+    a.thr = p->thr; a.primary = p->primary; a.secondary = p->secondary;
+    a.llr = llr; a.synd = synd; a.bits = bits; a.iters = iters; a.ok = ok; a.post = post; a.frame_clk = frame_clk;
+    {  // the chunk's arrays, in fpl_tile_words' order
+        const size_t c = (size_t)chunk, n = (size_t)g->n, m = (size_t)std::max(g->m, 1), E = (size_t)g->E;
+        uint64_t *at = w->fpl.get();
+        a.C = reinterpret_cast<double *>(at); at += c * E * FPL_LANES;
+        a.T = reinterpret_cast<double *>(at); at += c * n * FPL_LANES;
+        a.L = reinterpret_cast<double *>(at); at += c * n * FPL_LANES;
+        a.hard = at; at += c * n;
+        a.syn = at; at += c * m;
+        a.active = at; at += c;
+        a.flags = at;
+    }
+    {  // the deal: frames in the claim order's sequence (order.hip), so that a
+        // tile's 64 frames look alike; one tile, QLDPC_ORDER=0 or a shape the
+        // weights cannot run: index order.  Results are per frame either way.
+        const char *e = qldpc_diag_env("QLDPC_ORDER");
+        if (!(e && std::strcmp(e, "0") == 0) && batch > FPL_LANES) {
+            const hipError_t oe = launch_frame_order(g->n, g->m, dg->ell_col.get(), dg->row_deg.get(), batch, synd, llr,
+                                                     nullptr, nullptr, nullptr, w->fweight.get(), w->forder.get(),
+                                                     nullptr, stream);
+            if (oe == hipSuccess) a.frame_order = w->forder.get();
+            else (void)hipGetLastError();
+        }
+        w->order_count = a.frame_order ? batch : 0;
+    }
+    if (g->kernel_timing) {
+        if (!w->ev0) HIP_TRY(hipEventCreate(w->ev0.put()));
+        if (!w->ev1) HIP_TRY(hipEventCreate(w->ev1.put()));
+        HIP_TRY(hipEventRecord(w->ev0, stream));
+    }
+    if (before_decode) HIP_TRY(hipStreamWaitEvent(stream, before_decode, 0));
+    for (int t0 = 0; t0 < tiles_all; t0 += chunk) {
+        a.tiles = std::min(chunk, tiles_all - t0);
+        a.frame0 = t0 * FPL_LANES;
+        a.frames = std::min(batch - a.frame0, a.tiles * FPL_LANES);
+        HIP_TRY(launch_fpl_chunk(a, stream));
+    }
+    if (g->kernel_timing) {
+        HIP_TRY(hipEventRecord(w->ev1, stream));
+        w->ev_recorded = true;
+    }
+    return QLDPC_OK;
+}
+
 // Enqueue the decoder for `batch` device-resident frames on `stream`.  For the
 // V2 kernel the frames' palette + codes are taken from the stream's workspace
 // when `codes_ready` (written by build_frames), else computed here from llr.
@@ -281,6 +376,8 @@ int decode_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch,
               hipStream_t stream, bool codes_ready = false, uint64_t *frame_clk = nullptr,
               hipEvent_t before_decode = nullptr) {
     if (batch == 0) return QLDPC_OK;
+    if (g->variant == VAR_FPL)
+        return decode_fpl_on(g, dg, p, batch, llr, synd, bits, iters, ok, post, stream, frame_clk, before_decode);
     const int alg = p->algorithm;
     const bool v2 = g->variant == VAR_V2;
     const size_t lds = lds_of(*g, alg);
@@ -671,6 +768,25 @@ int qldpc_graph_create_host(int32_t n, int32_t m, const int32_t *row_ptr, const 
     return build_graph(n, m, row_ptr, col_idx, 0, out, true);
 }
 
+int qldpc_graph_create_opts(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *col_idx,
+                            const int32_t *col_ptr, const int32_t *row_idx, const int32_t *devices, int32_t ndevices,
+                            const qldpc_graph_opts *opts, qldpc_graph **out) {
+    const qldpc_graph_opts none{};
+    const qldpc_graph_opts &o = opts ? *opts : none;
+    if (o.layout != QLDPC_LAYOUT_AUTO && o.layout != QLDPC_LAYOUT_FRAME_PER_LANE)
+        return fail(QLDPC_EINVAL, "unknown layout " + std::to_string(o.layout));
+    for (int32_t r : o.reserved)
+        if (r) return fail(QLDPC_EINVAL, "qldpc_graph_opts.reserved must be zero");
+    if (!row_ptr || !col_idx) return fail(QLDPC_EINVAL, "NULL adjacency array");
+    if ((col_ptr == nullptr) != (row_idx == nullptr)) return fail(QLDPC_EINVAL, "col_ptr and row_idx go together");
+    if (n <= 0 || m < 0) return fail(QLDPC_EINVAL, "invalid graph dimensions");
+    if (o.host_only) return build_graph(n, m, row_ptr, col_idx, 0, out, true, nullptr, col_ptr, row_idx, o.layout);
+    if (!devices) return build_graph(n, m, row_ptr, col_idx, 0, out, false, nullptr, col_ptr, row_idx, o.layout);
+    if (ndevices <= 0 || ndevices > 64) return fail(QLDPC_EINVAL, "need 1..64 devices");
+    const std::vector<int> list(devices, devices + ndevices);
+    return build_graph(n, m, row_ptr, col_idx, 0, out, false, &list, col_ptr, row_idx, o.layout);
+}
+
 int qldpc_graph_labels(const qldpc_graph *g, int32_t *labels_out, int64_t *stats_out) {
     if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
     if (labels_out)
@@ -711,7 +827,9 @@ int qldpc_graph_plan(const qldpc_graph *g, int32_t device, int32_t algorithm, in
     if (variant)
         *variant = (g->variant == VAR_V2 && g->split_k > 1) ? "v2_split"
                    : (g->variant == VAR_V2 && g->v2RG > 0) ? "v2_hybrid" : variant_name(g->variant);
-    if (workgroups) {
+    if (workgroups && g->variant == VAR_FPL) {
+        *workgroups = fpl_cn_grid(g->fpl_class_off);  // the check-node pass's grid for one 64-frame tile
+    } else if (workgroups) {
         DeviceScope ds;
         if (int rc = ds.enter(dg->device)) return rc;
         int b = 0;

@@ -25,6 +25,7 @@ enum Variant : int {
     VAR_GLB_LDS = 1,  // messages in per-workgroup global scratch, totals/rows in LDS
     VAR_GLB_GLB = 2,  // everything per-frame in global scratch     (n = 100k)
     VAR_V2 = 3,       // wave-aligned register kernel (decoder_v2.hip)
+    VAR_FPL = 4,      // frame-per-lane: 64 frames per wave, a launch sequence per iteration (decoder_fpl.hip)
 };
 
 // Register slots per lane of the V2 instantiations.  (A third, 84 slots x 8
@@ -271,6 +272,70 @@ hipError_t launch_frame_order(int n, int m, const int32_t *ell_col, const int32_
                               const uint8_t *synd, const double *llr, const uint8_t *codes,
                               const double *palette, const uint8_t *pal_ok, int32_t *weight, int32_t *order,
                               const int32_t *col_orig, hipStream_t stream);
+// ---- frame-per-lane decoder (decoder_fpl.hip) ---------------------------------
+// A chunk of `tiles` tiles of 64 frames, lane = frame.  Per tile: messages
+// C[E][64] at bit_nodes (CSC) positions, totals T[n][64], channel LLRs
+// L[n][64], and one 64-bit lane mask per bit (hard decision) and per row
+// (target syndrome).  Tile t, slot s holds the frame at position
+// frame0 + 64 t + s of the deal (frame_order, or index order).
+constexpr int FPL_LANES = 64;
+constexpr int FPL_CN_WAVES = 4;   // rows per workgroup of the check-node pass
+constexpr int FPL_BIT_RUN = 4;    // consecutive bits per wave of the bit pass
+// Rows of at most this many edges keep their per-edge values (SPA: tanh(b/2),
+// min-sum: b) in registers between the two sweeps of the check-node pass;
+// longer rows stash them in C (SPA) or recompute them (min-sum).
+constexpr int FPL_ROW_CAP = 32;
+// The check-node pass is one launch per class of row lengths (0, <= 4, 8, 12,
+// 16, 24, 32 edges, longer), each instantiation with the registers its own
+// bucket needs: rows[] lists the rows by class, class c at
+// [class_off[c], class_off[c + 1]).
+constexpr int FPL_CLASSES = 8;
+constexpr int FPL_CLASS_CAP[FPL_CLASSES] = {0, 4, 8, 12, 16, 24, 32, 1 << 30};
+inline int fpl_row_class(int deg) {
+    int c = 0;
+    while (deg > FPL_CLASS_CAP[c]) ++c;
+    return c;
+}
+struct FplArgs {
+    int n, m, E;
+    const int32_t *rows;     // [m] rows by class
+    int class_off[FPL_CLASSES + 1];
+    const int32_t *row_ptr;  // [m + 1] check_nodes
+    const int32_t *col_idx;  // [E]
+    const int32_t *cslot;    // [E] position of the row-major edge in bit_nodes order
+    const int32_t *col_ptr;  // [n + 1] bit_nodes
+    int alg, max_it, thr_on;
+    double thr, primary, secondary;
+    int tiles, frames, frame0;   // this chunk: tiles, frames (<= 64 tiles), first deal position
+    const int32_t *frame_order;  // [batch] deal position -> frame; nullptr: index order
+    const double *llr;
+    const uint8_t *synd;
+    uint8_t *bits;
+    uint32_t *iters;
+    uint8_t *ok;
+    double *post;         // nullable
+    uint64_t *frame_clk;  // nullable
+    double *C, *T, *L;    // [tiles][E | n | n][64]
+    uint64_t *hard;       // [tiles][n]
+    uint64_t *syn;        // [tiles][m]
+    uint64_t *active;     // [tiles] lanes still decoding
+    uint64_t *flags;      // [tiles] lanes with a mismatched row in the pass just run
+};
+// Workspace bytes of one tile (8-byte units: doubles then masks).
+inline size_t fpl_tile_words(int n, int m, int E) {
+    return ((size_t)E + 2 * (size_t)n) * FPL_LANES + (size_t)n + (size_t)(m > 0 ? m : 1) + 2;
+}
+// Workgroups of the check-node pass for one tile: FPL_CN_WAVES rows each, per class.
+inline int fpl_cn_grid(const int *class_off) {
+    int g = 0;
+    for (int c = 0; c < FPL_CLASSES; ++c) g += (class_off[c + 1] - class_off[c] + FPL_CN_WAVES - 1) / FPL_CN_WAVES;
+    return g;
+}
+// Enqueue one chunk's whole decode: load transposes, max_it iterations of
+// (check-node pass, settle, bit pass), the closing parity / settle, store
+// transposes.  Nothing in it waits on another workgroup.
+hipError_t launch_fpl_chunk(const FplArgs &a, hipStream_t stream);
+
 hipError_t launch_math_selftest(int fn, int count, const double *in, double *out, hipStream_t stream);
 hipError_t launch_keys_match(int batch, int n, const uint8_t *alice, const uint8_t *bits,
                              uint8_t *match, hipStream_t stream);

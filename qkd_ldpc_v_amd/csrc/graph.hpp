@@ -143,6 +143,10 @@ struct Workspace {  // per (device, stream): frame counter + decoder scratch
     // graph's decoder reads llr[] (not V2), capacity in frames
     DevBuf<double> llr_ws;
     size_t llr_ws_frames = 0;
+    // frame-per-lane tiles (decoder_fpl.hip): messages, totals, LLRs and lane
+    // masks of one chunk, capacity in tiles
+    DevBuf<uint64_t> fpl;
+    size_t fpl_tiles = 0;
     // kernel timing (qldpc_set_kernel_timing): events around the last decode launch
     Event ev0, ev1;
     bool ev_recorded = false;
@@ -209,6 +213,8 @@ struct DeviceGraph {
     DevBuf<int32_t> col_orig, col_lab;  // V2 bank relabelling: label -> bit id, bit id -> label
     DevBuf<int32_t> ell_lab;     // row-ELL in labels (the claim order reads label-ordered frame codes)
     DevBuf<int32_t> pair_src, pair_col;  // v1 occurrence pairing (unsorted adjacency), [k][lane]
+    DevBuf<int32_t> fpl_row_ptr, fpl_col, fpl_cslot, fpl_col_ptr;  // frame-per-lane: CSR, bit_nodes position per edge, CSC starts
+    DevBuf<int32_t> fpl_rows;  // ... rows by length class
     std::mutex mu;     // workspaces (ws), occupancy cache
     std::map<void *, Workspace> ws;
     std::mutex io_mu;  // the host-buffer entry's staging buffers and stream, held copy-in .. copy-out
@@ -241,6 +247,7 @@ struct GraphTables {
     std::vector<uint32_t> vng_rec;
     std::vector<uint64_t> row_rmask;
     std::vector<int32_t> pair_src, pair_col, col_orig, col_lab, ell_lab;
+    std::vector<int32_t> fpl_row_ptr, fpl_col, fpl_cslot, fpl_col_ptr, fpl_rows;  // frame-per-lane graphs only (not in the digest)
 };
 
 }  // namespace qldpc
@@ -279,6 +286,7 @@ struct qldpc_graph {
     std::vector<int32_t> col_lab;           // V2 bank relabelling (relabel.cpp): bit id -> label; empty: identity
     long long relabel_stats[4] = {0, 0, 0, 0};  // bank excess before / after, busiest-bank cycles before / after
     std::vector<int> part_row0;             // V2 split: first layout row of each part (+ m)
+    int fpl_class_off[qldpc::FPL_CLASSES + 1] = {};  // frame-per-lane: rows by length class (GraphTables::fpl_rows)
     std::vector<std::unique_ptr<qldpc::DeviceGraph>> devs;
 };
 
@@ -290,9 +298,11 @@ void plan(qldpc_graph &g);
 bool plan_v2(qldpc_graph &g, const int32_t *row_ptr);
 bool plan_v2_split(qldpc_graph &g, const int32_t *row_ptr, const int32_t *col_idx);
 
-// layout.hip — validate, plan, build every table; touches no device
+// layout.hip — validate, plan, build every table; touches no device.  layout:
+// QLDPC_LAYOUT_AUTO (the planner's choice) or QLDPC_LAYOUT_FRAME_PER_LANE.
 int build_layout(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
-                 const int32_t *row_idx, std::unique_ptr<qldpc_graph> &out, GraphTables &t);
+                 const int32_t *row_idx, std::unique_ptr<qldpc_graph> &out, GraphTables &t,
+                 int layout = QLDPC_LAYOUT_AUTO);
 
 // capi.hip — used by run_trials.hip
 int check_params(const qldpc_params *p);

@@ -70,6 +70,7 @@ struct Layout {
     const int E;
     qldpc_graph *const g;
     GraphTables &t;
+    const int layout;  // QLDPC_LAYOUT_*
 
     // classify
     std::vector<int> dv;
@@ -677,9 +678,46 @@ struct Layout {
         }
     }
 
+    // Frame-per-lane (decoder_fpl.hip): the adjacency itself is the layout —
+    // CSR rows, each edge's position in bit_nodes order (the identity pairing:
+    // a bit's k-th message comes from the k-th row holding it) and the CSC
+    // starts.  Labels stay the reference's bit ids.
+    int build_fpl() {
+        if (g->paired)
+            return fail(QLDPC_EUNSUP, "the frame-per-lane layout needs ascending check_nodes rows and bit_nodes their "
+                                      "ascending transpose; this adjacency needs the reference's occurrence pairing "
+                                      "(v1 kernels, QLDPC_LAYOUT_AUTO)");
+        g->variant = VAR_FPL;
+        g->T = FPL_LANES;
+        g->EPL = 0;
+        for (int i = 0; i < n; ++i)
+            if (dv[i] == 0) t.iso_bits.push_back(i);
+        g->n_iso = (int)t.iso_bits.size();
+        t.fpl_row_ptr.assign(row_ptr, row_ptr + m + 1);
+        t.fpl_col.assign(col_idx, col_idx + E);
+        t.fpl_col_ptr.assign(n + 1, 0);
+        for (int i = 0; i < n; ++i) t.fpl_col_ptr[i + 1] = t.fpl_col_ptr[i] + dv[i];
+        t.fpl_cslot.resize(E);
+        std::vector<int> seen(n, 0);
+        for (int e = 0; e < E; ++e) t.fpl_cslot[e] = t.fpl_col_ptr[col_idx[e]] + seen[col_idx[e]]++;
+        // rows by length class, in row order inside a class (decoder.hpp FPL_CLASS_CAP)
+        for (int c = 0; c <= FPL_CLASSES; ++c) g->fpl_class_off[c] = 0;
+        for (int j = 0; j < m; ++j) ++g->fpl_class_off[fpl_row_class(row_ptr[j + 1] - row_ptr[j]) + 1];
+        for (int c = 0; c < FPL_CLASSES; ++c) g->fpl_class_off[c + 1] += g->fpl_class_off[c];
+        t.fpl_rows.resize(m);
+        {
+            std::vector<int> fill(g->fpl_class_off, g->fpl_class_off + FPL_CLASSES);
+            for (int j = 0; j < m; ++j) t.fpl_rows[fill[fpl_row_class(row_ptr[j + 1] - row_ptr[j])]++] = j;
+        }
+        row_ell();  // (the frame builders and the deal's weights read the row-ELL)
+        return QLDPC_OK;
+    }
+
     int build() {
         int rc;
-        if ((rc = classify()) || (rc = choose_plan())) return rc;
+        if ((rc = classify())) return rc;
+        if (layout == QLDPC_LAYOUT_FRAME_PER_LANE) return build_fpl();
+        if ((rc = choose_plan())) return rc;
         edge_order();
         relabel();
         vn_stage();
@@ -703,7 +741,7 @@ struct Layout {
 // bit_nodes (col_ptr / row_idx, the reference's H_matrix::bit_nodes in its
 // own order): NULL means the ascending transpose of check_nodes.
 int build_layout(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
-                 const int32_t *row_idx, std::unique_ptr<qldpc_graph> &out, GraphTables &t) {
+                 const int32_t *row_idx, std::unique_ptr<qldpc_graph> &out, GraphTables &t, int layout) {
     if (n <= 0 || m < 0 || !row_ptr || (!col_idx && row_ptr[m] > 0))
         return fail(QLDPC_EINVAL, "invalid graph dimensions or NULL arrays");
     if (n > MAX_N) return fail(QLDPC_EUNSUP, "n exceeds 2^20 bit nodes");
@@ -712,10 +750,14 @@ int build_layout(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *co
         if (row_ptr[j + 1] < row_ptr[j]) return fail(QLDPC_EINVAL, "row_ptr must be non-decreasing");
     const int E = row_ptr[m];
     if (E <= 0) return fail(QLDPC_EINVAL, "graph has no edges");
+    // QLDPC_VARIANT=fpl (diagnostic switch) selects the frame-per-lane layout as the option does
+    if (const char *want = qldpc_diag_env("QLDPC_VARIANT"))
+        if (std::strcmp(want, "fpl") == 0) layout = QLDPC_LAYOUT_FRAME_PER_LANE;
     // Empty check rows: before the first and after the last non-empty row only
     // (v1 decodes those; a lane's row counter steps by one per row start, so
-    // an empty row between two others is refused wherever it falls).
-    {
+    // an empty row between two others is refused wherever it falls).  The
+    // frame-per-lane layout walks rows by row_ptr and takes them anywhere.
+    if (layout != QLDPC_LAYOUT_FRAME_PER_LANE) {
         int first = 0, last = m - 1;
         while (row_ptr[first + 1] == row_ptr[first]) ++first;
         while (row_ptr[last + 1] == row_ptr[last]) --last;
@@ -728,7 +770,7 @@ int build_layout(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *co
     g->n = n;
     g->m = m;
     g->E = E;
-    Layout L{n, m, row_ptr, col_idx, col_ptr, row_idx, E, g.get(), t};
+    Layout L{n, m, row_ptr, col_idx, col_ptr, row_idx, E, g.get(), t, layout};
     if (int rc = L.build()) return rc;
     out = std::move(g);
     return QLDPC_OK;

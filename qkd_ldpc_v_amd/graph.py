@@ -149,19 +149,36 @@ class Graph:
     current one).  devices: an explicit list instead, one shard per entry
     (a device may repeat: concurrent shards on one GPU); decode() then splits a
     batch in len(devices) contiguous slices, one host thread each.
-    host_only: plan without touching a device (inspection; cannot decode)."""
+    host_only: plan without touching a device (inspection; cannot decode).
+    layout: "auto" (the planner's choice) or "frame_per_lane" — 64 frames per
+    wave and a launch sequence per iteration, no waiting between workgroups
+    (qldpc_graph_create_opts; canonical adjacency only)."""
 
-    def __init__(self, H: HMatrix, device_mask: int = 0, devices=None, host_only: bool = False):
+    def __init__(self, H: HMatrix, device_mask: int = 0, devices=None, host_only: bool = False,
+                 layout: str = "auto"):
         self.H = H
         self.n, self.m = H.n, H.m
         g = ctypes.c_void_p()
         self.host_only = bool(host_only)
-        if host_only and not _canonical_adjacency(H):
+        if layout not in _lib.LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(_lib.LAYOUTS)}")
+        self.layout = layout
+        if layout != "auto":
+            opts = _lib.qldpc_graph_opts(_lib.LAYOUTS[layout], 1 if host_only else 0)
+            if devices is None and device_mask:
+                devices = [d for d in range(31) if device_mask >> d & 1]
+            dl = None if devices is None else np.ascontiguousarray(devices, np.int32)
+            check(lib().qldpc_graph_create_opts(H.n, H.m, ptr(H.row_ptr), ptr(H.col_idx), ptr(H.col_ptr),
+                                                ptr(H.row_idx), ptr(dl), 0 if dl is None else int(dl.size),
+                                                ctypes.byref(opts), ctypes.byref(g)), "qldpc_graph_create_opts")
+        elif host_only and not _canonical_adjacency(H):
             # (the host-only planner takes check_nodes only and assumes bit_nodes
             # is their ascending transpose; the reference's occurrence pairing of
             # other lists needs qldpc_graph_create_checked)
             raise ValueError("unsorted adjacency: use Graph(H) / Graph(H, devices=...)")
-        if host_only:
+        if layout != "auto":
+            pass
+        elif host_only:
             check(lib().qldpc_graph_create_host(H.n, H.m, ptr(H.row_ptr), ptr(H.col_idx), ctypes.byref(g)),
                   "qldpc_graph_create_host")
         elif devices is not None:
