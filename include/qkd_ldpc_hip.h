@@ -284,6 +284,13 @@ const char *qldpc_last_error(void);
 /* Library version string. */
 const char *qldpc_version(void);
 
+/* Diagnostic, host only: the exit-gate threshold the next decode launch hands
+ * its kernel (the SPA register decoder runs a parity-only pass before a
+ * check-node scan when the scan before counted at most this many unsatisfied
+ * rows).  The library's constant, or QLDPC_EXIT_GATE under
+ * QLDPC_DIAG=1.  It moves work, never a result. */
+int32_t qldpc_exit_gate(void);
+
 /* Number of HIP devices visible to the process (the C++ drop-in's default
  * device list: every GPU of the node). */
 int qldpc_device_count(int32_t *count);

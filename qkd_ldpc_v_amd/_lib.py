@@ -121,6 +121,7 @@ _SIGNATURES = {
     "qldpc_device_count": (_I32, [_PI32]),
     "qldpc_last_error": (ctypes.c_char_p, []),
     "qldpc_version": (ctypes.c_char_p, []),
+    "qldpc_exit_gate": (_I32, []),
 }
 
 _lib = None

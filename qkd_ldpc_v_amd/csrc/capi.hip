@@ -277,6 +277,12 @@ int qldpc::split_check(qldpc_graph *g, DeviceGraph *dg, hipStream_t stream) {
 
 namespace {
 
+// DecodeArgs::exit_gate of a launch (decoder_v2.hip, the SPA register shapes'
+// parity-only pass): V2_EXIT_GATE, or QLDPC_EXIT_GATE under the diagnostic
+// switch (-1: never run the pass; INT_MAX: before every checked scan).  It
+// changes when the pass runs, never a result.
+int exit_gate() { return env_int("QLDPC_EXIT_GATE", V2_EXIT_GATE); }
+
 // Frame-per-lane workspace budget per (device, stream): a batch whose tiles
 // need more runs as consecutive chunks of tiles on the same stream.  4 GiB
 // holds 13-16 tiles (832-1024 frames) of the n = 102,400 codes.
@@ -526,6 +532,7 @@ int decode_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch,
         if (a.rows_wg_offset >= 0 && !a.vn_rows)
             return fail(QLDPC_EUNSUP, "this code's min-sum row aggregates need the bit gather (QLDPC_VNG=0 given)");
     }
+    a.exit_gate = exit_gate();
     if (v2 && !codes_ready)  // (relabelled graphs: the kernel reads a non-paletted frame by label)
         HIP_TRY(launch_palettize(g->n, a.nc, batch, llr, w->codes.get(), w->palette.get(), w->pal_ok.get(),
                                  dg->col_orig.get(), stream));
@@ -684,6 +691,8 @@ extern "C" {
 const char *qldpc_last_error(void) { return g_last_error.c_str(); }
 
 const char *qldpc_version(void) { return "qkd_ldpc_v_amd 0.1.0 (gfx950)"; }
+
+int32_t qldpc_exit_gate(void) { return exit_gate(); }
 
 int qldpc_device_count(int32_t *count) {
     if (!count) return fail(QLDPC_EINVAL, "count is NULL");

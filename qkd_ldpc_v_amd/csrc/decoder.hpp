@@ -64,11 +64,13 @@ constexpr __host__ __device__ int v2_threads_for(int R) { return R <= V2_R_SMALL
 // Phase ids of the diagnostic stamp build (QL_PHASE_STAMPS).
 enum StampId : int {
     ST_SETUP, ST_SETUP_WAIT, ST_S, ST_S_WAIT, ST_CN1, ST_CN1_WAIT, ST_CN2, ST_CN2_WAIT, ST_CN3,
-    ST_VN0, ST_VN0_WAIT, ST_VNK, ST_VNK_WAIT, ST_OUT, ST_OUT_WAIT, NUM_STAMPS
+    ST_VN0, ST_VN0_WAIT, ST_VNK, ST_VNK_WAIT, ST_OUT, ST_OUT_WAIT,
+    ST_GATE,  // the SPA exit gate's parity-only pass and its barrier wait
+    NUM_STAMPS
 };
 static const char *const STAMP_NAMES[NUM_STAMPS] = {
     "setup", "setup_wait", "synd", "synd_wait", "cn1", "cn1_wait", "cn2", "cn2_wait", "cn3",
-    "vn_init", "vn_init_wait", "vn_phases", "vn_phases_wait", "out", "out_wait"};
+    "vn_init", "vn_init_wait", "vn_phases", "vn_phases_wait", "out", "out_wait", "exit_pass"};
 
 struct DecodeArgs {
     // graph (device pointers; shared by every frame)
@@ -188,6 +190,12 @@ struct DecodeArgs {
     // at the frame's claim and at its results — the trial's own time inside the
     // batch (the reference times each trial's QKD_LDPC call, src/simulation.cpp:559-568)
     uint64_t *frame_clk;
+    // SPA, one-workgroup register shapes (decoder_v2.hip, GATE): a parity-only
+    // pass settles the exit test before the check-node scan of iteration it when
+    // the scan of iteration it - 1 counted at most this many rows off their
+    // syndrome bit, and at the iteration cap (< 0: never; the host's choice:
+    // graph.hpp V2_EXIT_GATE).  Speed only: no result depends on it.
+    int exit_gate;
 };
 
 // Frequency of s_memrealtime (gfx9: a constant 100 MHz clock).

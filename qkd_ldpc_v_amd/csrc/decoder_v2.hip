@@ -268,6 +268,21 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
     int *s_frame = reinterpret_cast<int *>(smem);
     int *s_flag = reinterpret_cast<int *>(smem) + 1;
     int *s_part = reinterpret_cast<int *>(smem) + 2;  // SPLIT: rank, sync slot
+    // SPA on ROWSCAN shapes: the exit gate.  A frame that leaves with
+    // iters = it leaves behind the scan of iteration it, whose tanh and row
+    // products nobody reads.  So each checked scan counts the rows off their
+    // syndrome bit, and when the count of the scan before is <= a.exit_gate
+    // (the frame is about to finish) a parity-only pass runs first: the
+    // decisions of the lane's slots and the scan's own row test, nothing
+    // written but a flag.  No row off: the frame leaves without that scan;
+    // otherwise the scan runs as ever.  At the iteration cap the pass stands in
+    // for the check-only scan.  Control words 2 and 3 are free here (s_part is
+    // SPLIT's, s_big min-sum's): the pass's mismatch epoch and the running sum
+    // of the scans' counts (never reset: a scan's count is the sum's growth,
+    // read behind the scan's barrier; the next adds come a barrier later).
+    constexpr bool GATE = ALG == 0 && ROWSCAN;
+    int *s_pflag = reinterpret_cast<int *>(smem) + 2;
+    uint32_t *s_nmis = reinterpret_cast<uint32_t *>(smem) + 3;
     double *total = reinterpret_cast<double *>(smem + V2_TOTAL_OFF);
     double *const rowA_lds = reinterpret_cast<double *>(smem + L.rows);    // SPA
     double2 *const rowAB_lds = reinterpret_cast<double2 *>(smem + L.rows); // min-sum
@@ -347,6 +362,13 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
     const int up = (lane == 0) ? 0 : lane - 1;
     int epoch = 0;
     if (tid == 0) *s_flag = 0;
+    uint32_t nmis_seen = 0;  // (GATE) *s_nmis behind the last scan's barrier
+    if constexpr (GATE) {
+        if (tid == 0) {
+            *s_pflag = 0;
+            *s_nmis = 0;
+        }
+    }
     // SPA: the expm1 class table of tanh_half_clip_t, once per workgroup (the
     // frame loop's first barrier orders it before any scan)
     // (two arrays of 16-byte entries: A at L.ctab, B right after A)
@@ -552,6 +574,9 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
 
         int iters = a.max_it, okv = 0;
         bool had_vn = false;
+        // (GATE) rows off their syndrome bit in the last checked scan; none yet:
+        // the first gate decision takes the count of the first checked scan
+        int gate_cnt = 0x7fffffff;
         // c2b starts at +0: iteration 0's b2c = tv - 0 with the clip at +inf is
         // the channel LLR itself, bitwise (the reference's unclipped
         // initialisation, :21-29), so the scan needs no iteration-0 select
@@ -912,6 +937,63 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
             }
             return false;
         };
+        // The row test behind a ROWSCAN scan's slot loop, shared with the exit
+        // gate's pass.  zA / zB: the decisions z_k = (total <= 0) of the lane's
+        // slots as the loop shifted them in.  Returns the rows started in this
+        // lane that miss their syndrome bit (GATE: how many; otherwise 0 / 1);
+        // hmr: whether the row finished here for the lane before misses its
+        // bit (meaningful where head > 0).
+        auto row_test = [&](uint32_t zA, uint32_t zB, int head, int row0, uint32_t sm, int &hmr) -> int {
+            int mis = 0;
+            // bit k of (zlo, zhi) = decision of slot k
+            const int na = epl < 32 ? epl : 32;
+            const uint32_t zlo = __builtin_bitreverse32(zA) >> (32 - na);
+            const uint32_t zhi = (epl > 32) ? (__builtin_bitreverse32(zB) >> (64 - epl)) : 0u;
+            // rows started in this lane: parity of the decisions under the
+            // row's slots vs its target syndrome bit (sm: bit j = j-th START)
+            int popen = 0;
+            const int rs0 = row0 + (head > 0 ? 1 : 0);
+            for (int j = 0; j < a.nst_max; ++j) {
+                if (j < nst) {
+                    const uint64_t mk = a.row_rmask[(size_t)j * T + tid];
+                    const int p = (__builtin_popcount(zlo & (uint32_t)mk) +
+                                   __builtin_popcount(zhi & (uint32_t)(mk >> 32) & 0x7fffffffu)) & 1;
+                    if (mk >> 63) {
+                        popen = p;  // continues in the next lane
+                    } else {
+                        const int mr = p ^ (int)((sm >> j) & 1u);
+                        if constexpr (GATE) mis += mr;
+                        else mis |= mr;
+                        if constexpr (ADAPT) {  // factor selector in min2's sign bit (:749-757)
+                            if (mr) reinterpret_cast<uint32_t *>(rowAB + rs0 + j)[3] |= 0x80000000u;
+                        }
+                    }
+                }
+            }
+            // a row split across two lanes of this wave: finished here
+            const int ppar = __shfl(popen, up, 64);
+            const int hpar = __builtin_popcount(zlo & ((1u << head) - 1u)) & 1;
+            hmr = ppar ^ hpar ^ s_row0;
+            return mis;
+        };
+        // The exit gate's pass (GATE): the scan's decisions and row test on the
+        // totals as they stand, and nothing else — no message, row product or
+        // total is touched.  Returns this lane's rows off their syndrome bit.
+        // (`<= 0.0` as everywhere: NaN and -0 decide as in the scan)
+        auto parity_pass = [&](int head, int row0, uint32_t sm) -> int {
+            uint32_t zA = 0, zB = 0;
+            meta.each_upto_tv(
+                epl, [&](uint32_t mt) -> double { return tot_at(mt); },
+                [&](int k, uint32_t, double tv) {
+                    const uint64_t zm = __builtin_amdgcn_ballot_w64(tv <= 0.0);
+                    if (k < 32) zA = add_carry(zA, zA, zm);
+                    else zB = add_carry(zB, zB, zm);
+                });
+            int hmr;
+            int c = row_test(zA, zB, head, row0, sm, hmr);
+            if (head > 0) c += hmr;
+            return c;
+        };
         int it0 = 0;
         if (ALG == 0 && fast0) {
             int head = head_in, row0 = row0_in;
@@ -976,6 +1058,23 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
             int head = head_in, row0 = row0_in;
             uint32_t sm = smask_f;
             asm volatile("" : "+v"(head), "+v"(row0), "+v"(sm));
+
+            // ---- exit gate (see GATE): the exit test alone, when the frame is
+            // about to finish or this is the cap's check-only iteration ----
+            if constexpr (GATE) {
+                if (check && a.exit_gate >= 0 && (!compute || gate_cnt <= a.exit_gate)) {
+                    if (parity_pass(head, row0, sm)) *s_pflag = epoch;
+                    __syncthreads();
+                    STAMP(ST_GATE);
+                    if (*s_pflag != epoch) {
+                        iters = it;
+                        okv = 1;
+                        break;
+                    }
+                    if (!compute) break;
+                    // some row is off: the full scan, which redoes the row test
+                }
+            }
 
             // ---- check-node scan: b2c, tanh / aggregates, row parity of z ----
             // A START begins a row (bit `sm & 1` of the target syndrome); an END
@@ -1067,33 +1166,9 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                     emk = emk_n;
                     pmk = pmk_n;
                 });
-                // bit k of (zlo, zhi) = decision of slot k
-                const int na = epl < 32 ? epl : 32;
-                const uint32_t zlo = __builtin_bitreverse32(zA) >> (32 - na);
-                const uint32_t zhi = (epl > 32) ? (__builtin_bitreverse32(zB) >> (64 - epl)) : 0u;
-                // rows started in this lane: parity of the decisions under the
-                // row's slots vs its target syndrome bit (sm: bit j = j-th START)
-                int popen = 0;
-                const int rs0 = row0 + (head > 0 ? 1 : 0);
-                for (int j = 0; j < a.nst_max; ++j) {
-                    if (j < nst) {
-                        const uint64_t mk = a.row_rmask[(size_t)j * T + tid];
-                        const int p = (__builtin_popcount(zlo & (uint32_t)mk) +
-                                       __builtin_popcount(zhi & (uint32_t)(mk >> 32) & 0x7fffffffu)) & 1;
-                        if (mk >> 63) {
-                            popen = p;  // continues in the next lane
-                        } else {
-                            const int mr = p ^ (int)((sm >> j) & 1u);
-                            mis |= mr;
-                            if constexpr (ADAPT) {  // factor selector in min2's sign bit (:749-757)
-                                if (mr) reinterpret_cast<uint32_t *>(rowAB + rs0 + j)[3] |= 0x80000000u;
-                            }
-                        }
-                    }
-                }
-                // a row split across two lanes of this wave: finished here
-                const int ppar = __shfl(popen, up, 64);
-                const int hpar = __builtin_popcount(zlo & ((1u << head) - 1u)) & 1;
+                // the rows' parities against their syndrome bits (row_test, above)
+                int hmr;
+                mis = row_test(zA, zB, head, row0, sm, hmr);
                 if constexpr (SPA_FAM) {
                     const double pacc = __shfl(acc, up, 64);
                     if (head > 0) {
@@ -1103,7 +1178,8 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                             if (k < head) p = p * c2b.get(k);
                         rowA[row0] = ql_exact::with_hi_word(p, ql_exact::hi_word(p) ^ syn[row0]);
                         if constexpr (ALG == 0) div_unsafe |= (__builtin_fabs(p) >= 0x1p-900) ? 0 : 1;
-                        mis |= ppar ^ hpar ^ s_row0;
+                        if constexpr (GATE) mis += hmr;
+                        else mis |= hmr;
                     }
                 } else {
                     MinAgg t;
@@ -1117,7 +1193,7 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                         h.m2 = ta.y;
                         h.neg = (int)(ql_exact::hi_word(ta.x) >> 31);
                         agg_merge(t, h);
-                        const int mr = ppar ^ hpar ^ s_row0;
+                        const int mr = hmr;
                         rowAB[row0] = ms_pack(t.m1, t.m2, s_row0 ^ t.neg, mr);
                         big |= (t.m2 > thr) ? 1 : 0;
                         mis |= mr;
@@ -1229,6 +1305,10 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                 if (mis) __hip_atomic_store(gmis, it + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
                 if (mis) *s_flag = epoch;
+                if constexpr (GATE) {  // the scan's count: few lanes hold a row that is off
+                    if (mis)
+                        __hip_atomic_fetch_add(s_nmis, (uint32_t)mis, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
                 if constexpr (!SPA_FAM) {
                     if (big) *s_big = epoch;
                 }
@@ -1248,6 +1328,13 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                                 : (*s_flag == epoch));
             if constexpr (!SPA_FAM)
                 msclip = a.thr_on && (SPLIT || !had_vn || a.ms_clip_later || *s_big == epoch);
+            if constexpr (GATE) {
+                // this scan's count = the sum's growth (an unchecked scan's is
+                // consumed, not used); the next scan adds a barrier from here
+                const uint32_t ns = __builtin_amdgcn_readfirstlane(*s_nmis);
+                gate_cnt = check ? (int)(ns - nmis_seen) : 0x7fffffff;
+                nmis_seen = ns;
+            }
             // SPA: rp / t by div_rn_safe when every t of this wave came out of
             // tanh's common path (|t| in [2^-55, 1]) and every row product of the
             // wave is at least 2^-900 in magnitude: the operand range where the

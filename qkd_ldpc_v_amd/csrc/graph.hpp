@@ -28,6 +28,12 @@ int hip_fail(hipError_t e, const char *what);
     } while (0)
 
 constexpr size_t LDS_LIMIT = 160 * 1024;
+// DecodeArgs::exit_gate of every launch (capi.hip exit_gate(); the SPA register
+// decoder's parity-only pass, decoder_v2.hip).  The smallest count that
+// precedes >= 99 % of the exits of C2's converging frames, measured with the
+// oracle on the bench's own trials (tools/exit_gate_stats.py, DESIGN.md §3.3:
+// 1024 C2 frames want 54, 4096 C1 frames 36 — a constant serves both).
+constexpr int V2_EXIT_GATE = 54;
 
 // ---- owners (move-only) -------------------------------------------------------
 // Device memory (hipMalloc / hipFree) or, Pinned, host memory the copies stay
