@@ -78,7 +78,7 @@ $(LIB): $(CSRC)/decoder.o $(CSRC)/decoder_v2.o $(CSRC)/decoder_fpl.o $(CSRC)/tri
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -lz -o $@
 
 # Diagnostic build with per-phase s_memtime stamps (never the product).  On the
-# host side only capi.hip (decode_on) reads QL_PHASE_STAMPS.
+# host side only capi.hip (PhaseStamps, a step of decode_on) reads QL_PHASE_STAMPS.
 STAMPLIB := $(PKG)/diag/libqkdldpc_hip.so
 stamps: $(STAMPLIB)
 $(CSRC)/decoder_st.o: $(CSRC)/decoder.hip $(CSRC)/decoder_common.hpp $(CSRC)/decoder.hpp $(CSRC)/exact_math.h

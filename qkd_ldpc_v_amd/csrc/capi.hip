@@ -42,30 +42,6 @@ int hip_fail(hipError_t e, const char *what) {
 
 namespace {
 
-const char *variant_name(int v) {
-    switch (v) {
-    case VAR_REG_LDS: return "reg_lds";
-    case VAR_GLB_LDS: return "glb_lds";
-    case VAR_V2: return "v2";
-    case VAR_FPL: return "fpl";
-    default: return "glb_glb";
-    }
-}
-
-// Threads per workgroup: the graph's lanes, or one part's for split frames.
-int block_threads(const qldpc_graph &g) {
-    return (g.variant == VAR_V2 && g.split_k > 1) ? g.split_pl : g.T;
-}
-
-size_t lds_of(const qldpc_graph &g, int alg) {
-    if (g.variant == VAR_FPL) return 0;  // (its transposes' LDS is static)
-    if (g.variant == VAR_V2 && g.split_k > 1)
-        return lds_bytes_v2(alg, g.n, g.split_mrows, g.split_pl, true, 0, 0, -1, g.split_cb);
-    return g.variant == VAR_V2 ? lds_bytes_v2(alg, g.n, g.m, g.T, false, g.v2R, g.v2RG,
-                                              (g.rows_global_ms && alg >= 2) ? g.rows_lds_ms : -1)
-                               : lds_bytes_for(g.variant, g.n, g.m, g.T);
-}
-
 // The graph's tables on the current device.  (pair_* and the label tables stay
 // NULL on graphs without them: the launches test the pointers.)
 int upload_tables(DeviceGraph &dg, const qldpc_graph &g, const GraphTables &t) {
@@ -197,18 +173,27 @@ long long v2_scratch_doubles(const qldpc_graph &g) {
 // Per-stream workspace of a device graph, created on first use.
 Workspace *workspace(DeviceGraph *dg, hipStream_t stream) { return &dg->ws[(void *)stream]; }
 
+// Workspace growth: buffers whose capacity `cap` is below `need` are
+// reallocated by `alloc` once the stream's work on the old ones has ended.  The
+// capacity reads 0 while they are invalid (an allocation failed).
+template <typename Alloc>
+int grow(size_t &cap, size_t need, hipStream_t stream, Alloc alloc) {
+    if (need <= cap) return QLDPC_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    cap = 0;
+    if (int rc = alloc()) return rc;
+    cap = need;
+    return QLDPC_OK;
+}
+
 // Ensure the workspace holds V2 frame codes for `batch` frames (caller holds dg->mu).
 int ensure_codes(qldpc_graph *g, Workspace *w, int batch, hipStream_t stream) {
-    if ((size_t)batch <= w->code_frames) return QLDPC_OK;
-    HIP_TRY(hipStreamSynchronize(stream));
-    w->code_frames = 0;
     const size_t nc = (size_t)(g->n + 3) / 4;
-    int rc;
-    if ((rc = w->codes.alloc((size_t)batch * nc)) || (rc = w->palette.alloc((size_t)batch * 4)) ||
-        (rc = w->pal_ok.alloc((size_t)batch)))
-        return rc;
-    w->code_frames = (size_t)batch;
-    return QLDPC_OK;
+    return grow(w->code_frames, (size_t)batch, stream, [&] {
+        int rc;
+        if ((rc = w->codes.alloc((size_t)batch * nc)) || (rc = w->palette.alloc((size_t)batch * 4))) return rc;
+        return w->pal_ok.alloc((size_t)batch);
+    });
 }
 
 // The device frame builders stage the frame's keys in LDS as bit words
@@ -257,6 +242,47 @@ SplitSerial &split_serial(int device) {
     return *p;
 }
 
+// One split launch's turn on its device: wait() makes the stream wait for the
+// launches it must not overlap, record() marks the end of this one.  The
+// device's lock is held from wait() until record() returns (or the turn ends).
+class SplitTurn {
+    SplitSerial *ser_ = nullptr;
+    std::unique_lock<std::mutex> lk_;
+    int slot_ = 0;
+    bool ok_ = false;
+    long long shape_ = -1;
+
+public:
+    int wait(int device, const LaunchShape &s, int wgs, int batch, hipStream_t stream) {
+        ser_ = &split_serial(device);
+        lk_ = std::unique_lock<std::mutex>(ser_->mu);
+        for (auto &e : ser_->ev)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        const int slots_per_xcd = wgs / 8;  // (8 XCDs; every workgroup of the device is launched)
+        // (batches of <= 2048 frames: a group that waits for the other launch to
+        // leave its XCD waits at most that launch's run — at 50 iterations of a
+        // C4 frame ~0.6 s — well inside the group timeout of ~4 s)
+        ok_ = 2 * (s.split_k - 1) < slots_per_xcd && batch <= 2048;
+        shape_ = ((long long)s.split_k << 48) | ((long long)s.part_lanes << 32) | (long long)s.lds_bytes;
+        if (ser_->last >= 0) {
+            const int prev = ser_->last, older = prev ^ 1;
+            if (ser_->shape[older] >= 0) HIP_TRY(hipStreamWaitEvent(stream, ser_->ev[older], 0));
+            if (!(ok_ && ser_->overlap_ok[prev] && ser_->shape[prev] == shape_))
+                HIP_TRY(hipStreamWaitEvent(stream, ser_->ev[prev], 0));
+        }
+        slot_ = ser_->last < 0 ? 0 : ser_->last ^ 1;
+        return QLDPC_OK;
+    }
+    int record(hipStream_t stream) {
+        HIP_TRY(hipEventRecord(ser_->ev[slot_], stream));
+        ser_->shape[slot_] = shape_;
+        ser_->overlap_ok[slot_] = ok_;
+        ser_->last = slot_;
+        lk_.unlock();
+        return QLDPC_OK;
+    }
+};
+
 }  // namespace
 
 // Split frames: after the stream is idle, fail loudly if a part group timed
@@ -288,173 +314,190 @@ int exit_gate() { return env_int("QLDPC_EXIT_GATE", V2_EXIT_GATE); }
 // holds 13-16 tiles (832-1024 frames) of the n = 102,400 codes.
 constexpr size_t FPL_BUDGET_BYTES = (size_t)4 << 30;
 
-// decode_on for a frame-per-lane graph: deal the frames to tiles of 64, then
-// enqueue every chunk's launch sequence (decoder_fpl.hip).  Nothing is read
-// back: the sequence's length depends on max_iterations and the graph alone.
-int decode_fpl_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch, const double *llr,
-                  const uint8_t *synd, uint8_t *bits, uint32_t *iters, uint8_t *ok, double *post, hipStream_t stream,
-                  uint64_t *frame_clk, hipEvent_t before_decode) {
-    const size_t tile_words = fpl_tile_words(g->n, g->m, g->E);
-    const int tiles_all = (batch + FPL_LANES - 1) / FPL_LANES;
-    int chunk = (int)std::min<size_t>((size_t)tiles_all, std::max<size_t>(1, FPL_BUDGET_BYTES / (tile_words * 8)));
-    {  // QLDPC_FPL_TILES=k (diagnostic switch): k tiles per chunk
-        const int k = env_int("QLDPC_FPL_TILES", 0);
-        if (k > 0) chunk = std::min(k, tiles_all);
-    }
-    chunk = std::min(chunk, 65535);  // (tiles are the grids' y dimension)
-    Workspace *w;
-    {
-        std::lock_guard<std::mutex> lk(dg->mu);
-        w = workspace(dg, stream);
-        int rc;
-        if ((size_t)chunk > w->fpl_tiles) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            w->fpl_tiles = 0;
-            if ((rc = w->fpl.alloc((size_t)chunk * tile_words))) return rc;
-            w->fpl_tiles = (size_t)chunk;
-        }
-        if ((size_t)batch > w->order_frames) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            w->order_frames = 0;
-            if ((rc = w->fweight.alloc((size_t)batch)) || (rc = w->forder.alloc((size_t)batch))) return rc;
-            w->order_frames = (size_t)batch;
+// The device-resident frames of one decode call (post, frame_clk: nullable).
+struct Frames {
+    int batch;
+    const double *llr;
+    const uint8_t *synd;
+    uint8_t *bits;
+    uint32_t *iters;
+    uint8_t *ok;
+    double *post;
+    uint64_t *frame_clk;
+};
+
+// ---- the steps of a decode call (decode_on, decode_fpl_on) ---------------------
+
+// Resident workgroups per CU of a launch on dg's device (the current one), 0
+// when its kernel cannot be resident.  Cached per algorithm: no launch-time
+// knob moves what occupancy_proxy() asks.  Caller holds dg->mu.
+int blocks_per_cu(DeviceGraph *dg, const LaunchShape &s, int *blocks) {
+    int &b = dg->occ[s.alg];
+    if (b == 0) {
+        const hipError_t e = s.variant == VAR_V2 ? occupancy_v2(s.occupancy_proxy(), &b)
+                                                 : occupancy(s.variant, s.alg, s.threads, s.lds_bytes, &b);
+        if (e != hipSuccess) {
+            b = 0;
+            return hip_fail(e, "occupancy");
         }
     }
-    FplArgs a{};
-    a.n = g->n; a.m = g->m; a.E = g->E;
-    a.row_ptr = dg->fpl_row_ptr.get(); a.col_idx = dg->fpl_col.get();
-    a.rows = dg->fpl_rows.get();
-    for (int c = 0; c <= FPL_CLASSES; ++c) a.class_off[c] = g->fpl_class_off[c];
-    a.cslot = dg->fpl_cslot.get(); a.col_ptr = dg->fpl_col_ptr.get();
-    a.alg = p->algorithm; a.max_it = p->max_iterations; a.thr_on = p->thr_enabled ? 1 : 0;
-    a.thr = p->thr; a.primary = p->primary; a.secondary = p->secondary;
-    a.llr = llr; a.synd = synd; a.bits = bits; a.iters = iters; a.ok = ok; a.post = post; a.frame_clk = frame_clk;
-    {  // the chunk's arrays, in fpl_tile_words' order
-        const size_t c = (size_t)chunk, n = (size_t)g->n, m = (size_t)std::max(g->m, 1), E = (size_t)g->E;
-        uint64_t *at = w->fpl.get();
-        a.C = reinterpret_cast<double *>(at); at += c * E * FPL_LANES;
-        a.T = reinterpret_cast<double *>(at); at += c * n * FPL_LANES;
-        a.L = reinterpret_cast<double *>(at); at += c * n * FPL_LANES;
-        a.hard = at; at += c * n;
-        a.syn = at; at += c * m;
-        a.active = at; at += c;
-        a.flags = at;
-    }
-    {  // the deal: frames in the claim order's sequence (order.hip), so that a
-        // tile's 64 frames look alike; one tile, QLDPC_ORDER=0 or a shape the
-        // weights cannot run: index order.  Results are per frame either way.
-        const char *e = qldpc_diag_env("QLDPC_ORDER");
-        if (!(e && std::strcmp(e, "0") == 0) && batch > FPL_LANES) {
-            const hipError_t oe = launch_frame_order(g->n, g->m, dg->ell_col.get(), dg->row_deg.get(), batch, synd, llr,
-                                                     nullptr, nullptr, nullptr, w->fweight.get(), w->forder.get(),
-                                                     nullptr, stream);
-            if (oe == hipSuccess) a.frame_order = w->forder.get();
-            else (void)hipGetLastError();
-        }
-        w->order_count = a.frame_order ? batch : 0;
-    }
-    if (g->kernel_timing) {
-        if (!w->ev0) HIP_TRY(hipEventCreate(w->ev0.put()));
-        if (!w->ev1) HIP_TRY(hipEventCreate(w->ev1.put()));
-        HIP_TRY(hipEventRecord(w->ev0, stream));
-    }
-    if (before_decode) HIP_TRY(hipStreamWaitEvent(stream, before_decode, 0));
-    for (int t0 = 0; t0 < tiles_all; t0 += chunk) {
-        a.tiles = std::min(chunk, tiles_all - t0);
-        a.frame0 = t0 * FPL_LANES;
-        a.frames = std::min(batch - a.frame0, a.tiles * FPL_LANES);
-        HIP_TRY(launch_fpl_chunk(a, stream));
-    }
-    if (g->kernel_timing) {
-        HIP_TRY(hipEventRecord(w->ev1, stream));
-        w->ev_recorded = true;
-    }
+    *blocks = b;
     return QLDPC_OK;
 }
 
-// Enqueue the decoder for `batch` device-resident frames on `stream`.  For the
-// V2 kernel the frames' palette + codes are taken from the stream's workspace
-// when `codes_ready` (written by build_frames), else computed here from llr.
-// The decode kernel waits for `before_decode` when given (the kernels that
-// prepare it do not).
-int decode_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch, const double *llr,
-              const uint8_t *synd, uint8_t *bits, uint32_t *iters, uint8_t *ok, double *post,
-              hipStream_t stream, bool codes_ready = false, uint64_t *frame_clk = nullptr,
-              hipEvent_t before_decode = nullptr) {
-    if (batch == 0) return QLDPC_OK;
-    if (g->variant == VAR_FPL)
-        return decode_fpl_on(g, dg, p, batch, llr, synd, bits, iters, ok, post, stream, frame_clk, before_decode);
-    const int alg = p->algorithm;
-    const bool v2 = g->variant == VAR_V2;
-    const size_t lds = lds_of(*g, alg);
-    Workspace *w;
-    int wgs;
+constexpr size_t split_ctl_words(size_t slots) { return 32 + 3 * 16 * slots; }
+
+// Workgroups of the launch, and the stream's workspace grown to hold `batch`
+// frames of it (a stream sync only when a buffer grows).
+int decode_workspace(qldpc_graph *g, DeviceGraph *dg, const LaunchShape &s, int batch, bool codes_ready,
+                     hipStream_t stream, Workspace **ws, int *workgroups) {
+    const bool v2 = s.variant == VAR_V2, split = s.split_k > 1;
+    std::lock_guard<std::mutex> lk(dg->mu);
+    int b = 0, rc;
+    if ((rc = blocks_per_cu(dg, s, &b))) return rc;
+    if (b <= 0) return fail(QLDPC_EUNSUP, "decoder kernel cannot be resident with this graph shape");
+    int wgs = std::min(batch, b * dg->num_cus);
+    // split frames: every workgroup of the device (each XCD must hold whole
+    // part groups; the claim protocol needs >= split_k of them per XCD)
+    if (split) {
+        wgs = b * dg->num_cus;
+        // QLDPC_SPLIT_WGS (A/B): fewer workgroups, so fewer frames share an
+        // XCD's L2 (whole XCD rounds of 8; every XCD keeps >= split_k)
+        const int lim = env_int("QLDPC_SPLIT_WGS", 0);
+        if (lim >= 8 * s.split_k && lim < wgs) wgs = lim - lim % 8;
+    }
+    Workspace *w = workspace(dg, stream);
+    if (!w->counter && (rc = w->counter.alloc(16))) return rc;
+    if (v2) {
+        if (codes_ready && (size_t)batch > w->code_frames)
+            return fail(QLDPC_EINVAL, "frame codes were not built for this batch");
+        if ((rc = ensure_codes(g, w, batch, stream))) return rc;
+    }
+    if (split && (rc = grow(w->split_frames, (size_t)batch, stream, [&] {
+            int r;
+            if ((r = w->split_ctl.alloc(split_ctl_words((size_t)batch + 64))) ||
+                (r = w->gtotal.alloc((size_t)batch * (g->n + 1))))
+                return r;
+            return w->gstage.alloc((size_t)batch * std::max<long long>(1, g->stage_doubles));
+        })))
+        return rc;
+    const size_t need = (size_t)(v2 ? v2_scratch_doubles(*g) : v1_scratch_doubles(*g)) * (size_t)wgs;
+    if ((rc = grow(w->scratch_doubles, need, stream, [&] { return w->scratch.alloc(need); }))) return rc;
+    *ws = w;
+    *workgroups = wgs;
+    return QLDPC_OK;
+}
+
+// The frame-per-lane decoder's workspace, grown to `chunk` tiles.
+int fpl_workspace(DeviceGraph *dg, size_t chunk, size_t tile_words, hipStream_t stream, Workspace **ws) {
+    std::lock_guard<std::mutex> lk(dg->mu);
+    Workspace *w = workspace(dg, stream);
+    *ws = w;
+    return grow(w->fpl_tiles, chunk, stream, [&] { return w->fpl.alloc(chunk * tile_words); });
+}
+
+// Claim order: hardest-looking frames first (order.hip), for batches of at
+// least min_batch frames; QLDPC_ORDER=0: index order.  It only schedules —
+// results never depend on it — so a shape it cannot run (LDS beyond the device
+// limit) decodes in index order instead.  *order: the order, or nullptr.
+int claim_order(const qldpc_graph *g, DeviceGraph *dg, Workspace *w, const Frames &f, int min_batch,
+                hipStream_t stream, const int32_t **order) {
+    const size_t batch = (size_t)f.batch;
     {
         std::lock_guard<std::mutex> lk(dg->mu);
-        if (dg->occ[alg] == 0) {
-            int b = 0;
-            if (v2) HIP_TRY(occupancy_v2(g->v2R, g->v2RG, g->split_k, alg, block_threads(*g), lds, &b));
-            else HIP_TRY(occupancy(g->variant, alg, g->T, lds, &b));
-            if (b <= 0) return fail(QLDPC_EUNSUP, "decoder kernel cannot be resident with this graph shape");
-            dg->occ[alg] = b;
-        }
-        wgs = std::min(batch, dg->occ[alg] * dg->num_cus);
-        // split frames: every workgroup of the device (each XCD must hold whole
-        // part groups; the claim protocol needs >= split_k of them per XCD)
-        if (v2 && g->split_k > 1) {
-            wgs = dg->occ[alg] * dg->num_cus;
-            // QLDPC_SPLIT_WGS (A/B): fewer workgroups, so fewer frames share an
-            // XCD's L2 (whole XCD rounds of 8; every XCD keeps >= split_k)
-            const int lim = env_int("QLDPC_SPLIT_WGS", 0);
-            if (lim >= 8 * g->split_k && lim < wgs) wgs = lim - lim % 8;
-        }
-        w = workspace(dg, stream);
-        int rc;
-        if (!w->counter && (rc = w->counter.alloc(16))) return rc;
-        if (v2) {
-            if (codes_ready && (size_t)batch > w->code_frames)
-                return fail(QLDPC_EINVAL, "frame codes were not built for this batch");
-            if ((rc = ensure_codes(g, w, batch, stream))) return rc;
-            if (g->split_k > 1 && (size_t)batch > w->split_frames) {
-                HIP_TRY(hipStreamSynchronize(stream));
-                w->split_frames = 0;
-                const size_t slots = (size_t)batch + 64;
-                if ((rc = w->split_ctl.alloc(32 + 3 * 16 * slots)) ||
-                    (rc = w->gtotal.alloc((size_t)batch * (g->n + 1))) ||
-                    (rc = w->gstage.alloc((size_t)batch * std::max<long long>(1, g->stage_doubles))))
-                    return rc;
-                w->split_frames = (size_t)batch;
-            }
-        }
-        if ((size_t)batch > w->order_frames) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            w->order_frames = 0;
-            if ((rc = w->fweight.alloc((size_t)batch)) || (rc = w->forder.alloc((size_t)batch))) return rc;
-            w->order_frames = (size_t)batch;
-        }
-        {
-            const long long per = v2 ? v2_scratch_doubles(*g) : v1_scratch_doubles(*g);
-            const size_t need = (size_t)per * (size_t)wgs;
-            if (need > w->scratch_doubles) {
-                if (w->scratch) HIP_TRY(hipStreamSynchronize(stream));
-                if ((rc = w->scratch.alloc(need))) return rc;
-                w->scratch_doubles = need;
-            }
-        }
+        if (int rc = grow(w->order_frames, batch, stream, [&] {
+                const int r = w->fweight.alloc(batch);
+                return r ? r : w->forder.alloc(batch);
+            }))
+            return rc;
     }
+    *order = nullptr;
+    const char *e = qldpc_diag_env("QLDPC_ORDER");
+    if (!(e && std::strcmp(e, "0") == 0) && f.batch >= min_batch) {
+        // (V2 reads the frame codes; on relabelled graphs they are in label order, so is the row-ELL it reads)
+        const bool v2 = g->variant == VAR_V2;
+        const hipError_t oe = launch_frame_order(
+            g->n, g->m, dg->col_orig ? dg->ell_lab.get() : dg->ell_col.get(), dg->row_deg.get(), f.batch, f.synd, f.llr,
+            v2 ? w->codes.get() : nullptr, v2 ? w->palette.get() : nullptr, v2 ? w->pal_ok.get() : nullptr,
+            w->fweight.get(), w->forder.get(), dg->col_orig.get(), stream);
+        if (oe == hipSuccess) *order = w->forder.get();
+        else (void)hipGetLastError();  // clear the sticky launch error; index order
+    }
+    w->order_count = *order ? f.batch : 0;
+    return QLDPC_OK;
+}
+
+// Timing bracket (qldpc_set_kernel_timing): events around the decode launches.
+// (The workspace is per stream: no other call records on these events.)
+int timing_begin(const qldpc_graph *g, Workspace *w, hipStream_t stream) {
+    if (!g->kernel_timing) return QLDPC_OK;
+    if (!w->ev0) HIP_TRY(hipEventCreate(w->ev0.put()));
+    if (!w->ev1) HIP_TRY(hipEventCreate(w->ev1.put()));
+    HIP_TRY(hipEventRecord(w->ev0, stream));
+    return QLDPC_OK;
+}
+int timing_end(const qldpc_graph *g, Workspace *w, hipStream_t stream) {
+    if (!g->kernel_timing) return QLDPC_OK;
+    HIP_TRY(hipEventRecord(w->ev1, stream));
+    w->ev_recorded = true;
+    return QLDPC_OK;
+}
+
+// Diagnostic stamp build (QL_PHASE_STAMPS, never the product): the launch's
+// per-wave phase stamps, reported as each phase's share of wave time in one
+// JSON line on stderr.  The product's is empty.
+struct PhaseStamps {
+#ifdef QL_PHASE_STAMPS
+    DevBuf<uint64_t> d_st;
+    size_t nst = 0;
+    int begin(DecodeArgs &a, int wgs, int threads, hipStream_t stream) {
+        nst = (size_t)wgs * (threads / 64) * NUM_STAMPS;
+        if (int rc = d_st.alloc(nst)) return rc;
+        HIP_TRY(hipMemsetAsync(d_st.get(), 0, nst * sizeof(uint64_t), stream));
+        a.stamps = d_st.get();
+        return QLDPC_OK;
+    }
+    int report(hipStream_t stream) {
+        std::vector<uint64_t> h(nst);
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(h.data(), d_st.get(), nst * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        double tot[NUM_STAMPS] = {0}, all = 0;
+        for (size_t i = 0; i < nst; ++i) tot[i % NUM_STAMPS] += (double)h[i];
+        for (int i = 0; i < NUM_STAMPS; ++i) all += tot[i];
+        std::string js = "{\"phase_stamps\": {";
+        for (int i = 0; i < NUM_STAMPS; ++i)
+            js += std::string(i ? ", " : "") + "\"" + STAMP_NAMES[i] + "\": " + std::to_string(all > 0 ? tot[i] / all : 0.);
+        js += "}, \"wave_cycles_total\": " + std::to_string(all) + "}";
+        fprintf(stderr, "%s\n", js.c_str());
+        return QLDPC_OK;
+    }
+#else
+    int begin(DecodeArgs &, int, int, hipStream_t) { return QLDPC_OK; }
+    int report(hipStream_t) { return QLDPC_OK; }
+#endif
+};
+
+// The kernel arguments of a V1 / V2 launch: what the shape chose decides every
+// table and offset here (frame_order is the claim-order step's).
+DecodeArgs fill_args(const qldpc_graph *g, const DeviceGraph *dg, const Workspace *w, const LaunchShape &s,
+                     const qldpc_params *p, const Frames &f) {
+    const int alg = s.alg;
+    const bool v2 = s.variant == VAR_V2, split = s.split_k > 1;
+    const bool minsum = v2 && alg >= 2;  // V2 min-sum: the tables that list a bit's rows by kpos
     DecodeArgs a{};
-    a.n = g->n; a.m = g->m; a.E = g->E; a.T = block_threads(*g); a.EPL = g->EPL; a.dv_max = g->dv_max; a.max_dc = g->max_dc;
-    a.slot_meta = dg->slot_meta.get(); a.lane_row0 = dg->lane_row0.get(); a.lane_head = dg->lane_head.get();
+    a.n = g->n; a.m = g->m; a.E = g->E; a.T = s.threads; a.EPL = g->EPL; a.dv_max = g->dv_max; a.max_dc = g->max_dc;
+    a.lane_row0 = dg->lane_row0.get(); a.lane_head = dg->lane_head.get();
     a.lane_nst = dg->lane_nst.get(); a.lane_epl = dg->lane_epl.get();
-    if (v2 && alg >= 2) a.slot_meta = dg->slot_meta_ms.get();
-    a.vn_mask = (v2 && alg >= 2) ? dg->vn_mask_ms.get() : dg->vn_mask.get();
-    a.vn_exec = (v2 && alg >= 2) ? dg->vn_exec_ms.get() : dg->vn_exec.get();
+    a.slot_meta = minsum ? dg->slot_meta_ms.get() : dg->slot_meta.get();
+    a.vn_mask = minsum ? dg->vn_mask_ms.get() : dg->vn_mask.get();
+    a.vn_exec = minsum ? dg->vn_exec_ms.get() : dg->vn_exec.get();
+    a.slot_meta2 = minsum ? dg->slot_meta2_ms.get() : dg->slot_meta2.get();
     a.ell_col = dg->ell_col.get(); a.row_deg = dg->row_deg.get();
     a.alg = alg; a.max_it = p->max_iterations; a.thr_on = p->thr_enabled ? 1 : 0;
     a.thr = p->thr; a.primary = p->primary; a.secondary = p->secondary;
     {
         const bool norm = alg == 2 || alg == 4, adapt = alg == 4 || alg == 5;
-        const auto fine = [&](double f) { return norm ? (std::fabs(f) <= 1.0) : (f >= 0.0); };  // NaN: not fine
+        const auto fine = [&](double x) { return norm ? (std::fabs(x) <= 1.0) : (x >= 0.0); };  // NaN: not fine
         a.ms_clip_later = (fine(p->primary) && (!adapt || fine(p->secondary))) ? 0 : 1;
     }
     {
@@ -462,7 +505,8 @@ int decode_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch,
         a.spa_tlim = std::tanh(lim / 2.);
         a.spa_ctop = 2. * std::atanh(0x1.fffffffffffffp-1);
     }
-    a.batch = batch; a.llr = llr; a.synd = synd; a.bits = bits; a.iters = iters; a.ok = ok; a.post = post;
+    a.batch = f.batch; a.llr = f.llr; a.synd = f.synd; a.bits = f.bits; a.iters = f.iters; a.ok = f.ok; a.post = f.post;
+    a.frame_clk = f.frame_clk;
     a.frame_counter = w->counter.get();
     a.scratch = w->scratch.get();
     a.scratch_wg_doubles = v2 ? v2_scratch_doubles(*g) : v1_scratch_doubles(*g);
@@ -474,28 +518,26 @@ int decode_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch,
     a.hd_uniform_dv = g->hd_uniform_dv;
     a.vn_k0 = g->vn_k0; a.n_hd = g->n_hd; a.hd_bits = dg->hd_bits.get(); a.hd_dv = dg->hd_dv.get();
     a.stage_off = dg->stage_off.get();
-    a.slot_meta2 = (v2 && alg >= 2) ? dg->slot_meta2_ms.get() : dg->slot_meta2.get();
     a.stage_wg_offset = (long long)g->v2RG * REG_TSTRIDE;
-    a.rows_wg_offset = (v2 && g->rows_global_ms && alg >= 2) ? v2_rows_offset(*g) : -1;
-    a.rows_lds = (v2 && g->rows_global_ms && alg >= 2) ? g->rows_lds_ms : g->m;
-    a.rows_lds_waves = (v2 && g->rows_global_ms && alg >= 2) ? g->rows_lds_waves_ms : (g->T / 64);
+    a.rows_wg_offset = s.rglb ? v2_rows_offset(*g) : -1;
+    a.rows_lds = s.rglb ? s.rows_lds : g->m;
+    a.rows_lds_waves = s.rglb ? g->rows_lds_waves_ms : (g->T / 64);
     a.wave_rows = dg->wave_rows.get();
     // the rows kept in global scratch fit the totals region below total[n]
     // (dead between the scan and the bit gather): their waves' message pass
     // reads them from an LDS copy (QLDPC_ROWS_COPY=0: from L2, A/B)
-    a.rows_copy = (a.rows_wg_offset >= 0 && (long long)(g->m - a.rows_lds) * 16 <= (long long)g->n * 8 &&
+    a.rows_copy = (s.rglb && (long long)(g->m - a.rows_lds) * 16 <= (long long)g->n * 8 &&
                    env_int("QLDPC_ROWS_COPY", 1))
                       ? 1 : 0;
     a.row_orig = dg->row_orig.get();
     a.col_orig = dg->col_orig.get();
     a.col_lab = dg->col_lab.get();
     a.llr_lab_wg_offset = (v2 && dg->col_orig) ? v2_llr_lab_offset(*g) : -1;
-    a.frame_clk = frame_clk;
     a.row_sem = (v2 && g->nst_max > 0) ? dg->row_sem.get() : nullptr;
     a.row_rmask = (v2 && g->nst_max > 0) ? dg->row_rmask.get() : nullptr;
     a.nst_max = g->nst_max;
-    a.split_k = v2 ? g->split_k : 1;
-    if (v2 && g->split_k > 1) {
+    a.split_k = s.split_k;
+    if (split) {
         const int slots = (int)w->split_frames + 64;
         a.split_mrows = g->split_mrows;
         a.split_slots = slots;
@@ -511,113 +553,118 @@ int decode_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch,
         a.split_cb = g->split_cb;
         a.split_nc = g->split_nc;
         a.xoff = g->split_cb > 0 ? dg->xoff.get() : nullptr;
-        a.xbit = alg >= 2 ? dg->xbit_ms.get() : dg->xbit.get();
-        HIP_TRY(hipMemsetAsync(w->split_ctl.get(), 0, (32 + 3 * 16 * (size_t)slots) * sizeof(int), stream));
+        a.xbit = minsum ? dg->xbit_ms.get() : dg->xbit.get();
     }
     a.nc = (g->n + 3) / 4;
     a.codes = w->codes.get(); a.palette = w->palette.get(); a.pal_ok = w->pal_ok.get();
     a.n_iso = g->n_iso; a.iso_bits = dg->iso_bits.get(); a.v2R = g->v2R; a.v2RG = g->v2RG;
-    {  // min-sum bit gather where the shape allows it (QLDPC_VNG=0: VN phases instead)
-        const char *e = qldpc_diag_env("QLDPC_VNG");
-        const bool off = e && std::strcmp(e, "0") == 0;
-        if (v2 && g->vng && !off && v2_vng_ok(alg, g->v2R, g->v2RG, a.split_k, g->dv_max, g->m)) {
-            a.vn_rows = reinterpret_cast<const uint2 *>(dg->vn_rows.get());
-            if (g->v2RG > 0) {
-                a.vng_bits = reinterpret_cast<const uint2 *>(dg->vng_bits.get());
-                a.slot_meta2 = dg->vng_meta2.get();
-            } else {
-                a.slot_meta2 = dg->vng_rec.get();
-            }
+    if (s.vng) {  // min-sum bit gather instead of the VN phases
+        a.vn_rows = reinterpret_cast<const uint2 *>(dg->vn_rows.get());
+        if (s.RG > 0) {
+            a.vng_bits = reinterpret_cast<const uint2 *>(dg->vng_bits.get());
+            a.slot_meta2 = dg->vng_meta2.get();
+        } else {
+            a.slot_meta2 = dg->vng_rec.get();
         }
-        if (a.rows_wg_offset >= 0 && !a.vn_rows)
-            return fail(QLDPC_EUNSUP, "this code's min-sum row aggregates need the bit gather (QLDPC_VNG=0 given)");
     }
     a.exit_gate = exit_gate();
+    return a;
+}
+
+// The kernel arguments of a frame-per-lane chunk sequence (tiles / frames / frame0 are each chunk's).
+FplArgs fill_fpl_args(const qldpc_graph *g, const DeviceGraph *dg, const Workspace *w, const qldpc_params *p,
+                      const Frames &f, size_t chunk) {
+    FplArgs a{};
+    a.n = g->n; a.m = g->m; a.E = g->E;
+    a.row_ptr = dg->fpl_row_ptr.get(); a.col_idx = dg->fpl_col.get();
+    a.rows = dg->fpl_rows.get();
+    for (int c = 0; c <= FPL_CLASSES; ++c) a.class_off[c] = g->fpl_class_off[c];
+    a.cslot = dg->fpl_cslot.get(); a.col_ptr = dg->fpl_col_ptr.get();
+    a.alg = p->algorithm; a.max_it = p->max_iterations; a.thr_on = p->thr_enabled ? 1 : 0;
+    a.thr = p->thr; a.primary = p->primary; a.secondary = p->secondary;
+    a.llr = f.llr; a.synd = f.synd; a.bits = f.bits; a.iters = f.iters; a.ok = f.ok; a.post = f.post;
+    a.frame_clk = f.frame_clk;
+    // the chunk's arrays, in fpl_tile_words' order
+    const size_t c = chunk, n = (size_t)g->n, m = (size_t)std::max(g->m, 1), E = (size_t)g->E;
+    uint64_t *at = w->fpl.get();
+    a.C = reinterpret_cast<double *>(at); at += c * E * FPL_LANES;
+    a.T = reinterpret_cast<double *>(at); at += c * n * FPL_LANES;
+    a.L = reinterpret_cast<double *>(at); at += c * n * FPL_LANES;
+    a.hard = at; at += c * n;
+    a.syn = at; at += c * m;
+    a.active = at; at += c;
+    a.flags = at;
+    return a;
+}
+
+// decode_on for a frame-per-lane graph: deal the frames to tiles of 64, then
+// enqueue every chunk's launch sequence (decoder_fpl.hip).  Nothing is read
+// back: the sequence's length depends on max_iterations and the graph alone.
+int decode_fpl_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, const Frames &f, hipStream_t stream,
+                  hipEvent_t before_decode) {
+    const size_t tile_words = fpl_tile_words(g->n, g->m, g->E);
+    const int tiles_all = (f.batch + FPL_LANES - 1) / FPL_LANES;
+    int chunk = (int)std::min<size_t>((size_t)tiles_all, std::max<size_t>(1, FPL_BUDGET_BYTES / (tile_words * 8)));
+    {  // QLDPC_FPL_TILES=k (diagnostic switch): k tiles per chunk
+        const int k = env_int("QLDPC_FPL_TILES", 0);
+        if (k > 0) chunk = std::min(k, tiles_all);
+    }
+    chunk = std::min(chunk, 65535);  // (tiles are the grids' y dimension)
+    Workspace *w;
+    int rc;
+    if ((rc = fpl_workspace(dg, (size_t)chunk, tile_words, stream, &w))) return rc;
+    FplArgs a = fill_fpl_args(g, dg, w, p, f, (size_t)chunk);
+    // the deal: frames in the claim order's sequence, so that a tile's 64 frames
+    // look alike (one tile: index order).  Results are per frame either way.
+    if ((rc = claim_order(g, dg, w, f, FPL_LANES + 1, stream, &a.frame_order))) return rc;
+    if ((rc = timing_begin(g, w, stream))) return rc;
+    if (before_decode) HIP_TRY(hipStreamWaitEvent(stream, before_decode, 0));
+    for (int t0 = 0; t0 < tiles_all; t0 += chunk) {
+        a.tiles = std::min(chunk, tiles_all - t0);
+        a.frame0 = t0 * FPL_LANES;
+        a.frames = std::min(f.batch - a.frame0, a.tiles * FPL_LANES);
+        HIP_TRY(launch_fpl_chunk(a, stream));
+    }
+    return timing_end(g, w, stream);
+}
+
+// Enqueue the decoder for `batch` device-resident frames on `stream`.  For the
+// V2 kernel the frames' palette + codes are taken from the stream's workspace
+// when `codes_ready` (written by build_frames), else computed here from llr.
+// The decode kernel waits for `before_decode` when given (the kernels that
+// prepare it do not).
+int decode_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch, const double *llr,
+              const uint8_t *synd, uint8_t *bits, uint32_t *iters, uint8_t *ok, double *post,
+              hipStream_t stream, bool codes_ready = false, uint64_t *frame_clk = nullptr,
+              hipEvent_t before_decode = nullptr) {
+    if (batch == 0) return QLDPC_OK;
+    const Frames f{batch, llr, synd, bits, iters, ok, post, frame_clk};
+    if (g->variant == VAR_FPL) return decode_fpl_on(g, dg, p, f, stream, before_decode);
+    const LaunchShape s = launch_shape(*g, p->algorithm, vng_enabled());  // (per call: the knobs are read at launch)
+    if (s.rglb && !s.vng)
+        return fail(QLDPC_EUNSUP, "this code's min-sum row aggregates need the bit gather (QLDPC_VNG=0 given)");
+    const bool v2 = s.variant == VAR_V2, split = s.split_k > 1;
+    Workspace *w;
+    int wgs, rc;
+    if ((rc = decode_workspace(g, dg, s, batch, codes_ready, stream, &w, &wgs))) return rc;
+    DecodeArgs a = fill_args(g, dg, w, s, p, f);
+    if (split) HIP_TRY(hipMemsetAsync(w->split_ctl.get(), 0, split_ctl_words(a.split_slots) * sizeof(int), stream));
     if (v2 && !codes_ready)  // (relabelled graphs: the kernel reads a non-paletted frame by label)
         HIP_TRY(launch_palettize(g->n, a.nc, batch, llr, w->codes.get(), w->palette.get(), w->pal_ok.get(),
                                  dg->col_orig.get(), stream));
-    {  // claim order: hardest-looking frames first (order.hip; QLDPC_ORDER=0: index order).
-        // It only schedules — results never depend on it — so a shape it cannot
-        // run (LDS beyond the device limit) decodes in index order instead.
-        const char *e = qldpc_diag_env("QLDPC_ORDER");
-        if (!(e && std::strcmp(e, "0") == 0) && batch > 1) {
-            // (relabelled graphs: the frame codes are in label order, so is the row-ELL it reads)
-            const hipError_t oe = launch_frame_order(g->n, g->m, dg->col_orig ? dg->ell_lab.get() : dg->ell_col.get(),
-                                                     dg->row_deg.get(), batch, synd, llr,
-                                                     v2 ? w->codes.get() : nullptr, w->palette.get(), w->pal_ok.get(),
-                                                     w->fweight.get(), w->forder.get(), dg->col_orig.get(), stream);
-            if (oe == hipSuccess) a.frame_order = w->forder.get();
-            else (void)hipGetLastError();  // clear the sticky launch error; index order
-        }
-        w->order_count = a.frame_order ? batch : 0;
-    }
+    if ((rc = claim_order(g, dg, w, f, 2, stream, &a.frame_order))) return rc;
     HIP_TRY(hipMemsetAsync(w->counter.get(), 0, sizeof(int), stream));
-#ifdef QL_PHASE_STAMPS
-    const size_t nst = (size_t)wgs * (block_threads(*g) / 64) * NUM_STAMPS;
-    DevBuf<uint64_t> d_st;
-    if (int rc = d_st.alloc(nst)) return rc;
-    HIP_TRY(hipMemsetAsync(d_st.get(), 0, nst * sizeof(uint64_t), stream));
-    a.stamps = d_st.get();
-#endif
-    std::unique_lock<std::mutex> split_lk;
-    SplitSerial *ser = nullptr;
-    int ser_slot = 0;
-    bool ser_ok = false;
-    long long ser_shape = -1;
-    if (v2 && g->split_k > 1) {  // split launches in flight per device (above)
-        ser = &split_serial(dg->device);
-        split_lk = std::unique_lock<std::mutex>(ser->mu);
-        for (auto &e : ser->ev)
-            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        const int slots_per_xcd = wgs / 8;  // (8 XCDs; every workgroup of the device is launched)
-        // (batches of <= 2048 frames: a group that waits for the other launch to
-        // leave its XCD waits at most that launch's run — at 50 iterations of a
-        // C4 frame ~0.6 s — well inside the group timeout of ~4 s)
-        ser_ok = 2 * (g->split_k - 1) < slots_per_xcd && batch <= 2048;
-        ser_shape = ((long long)g->split_k << 48) | ((long long)g->split_pl << 32) | (long long)lds;
-        if (ser->last >= 0) {
-            const int prev = ser->last, older = prev ^ 1;
-            if (ser->shape[older] >= 0) HIP_TRY(hipStreamWaitEvent(stream, ser->ev[older], 0));
-            if (!(ser_ok && ser->overlap_ok[prev] && ser->shape[prev] == ser_shape))
-                HIP_TRY(hipStreamWaitEvent(stream, ser->ev[prev], 0));
-        }
-        ser_slot = ser->last < 0 ? 0 : ser->last ^ 1;
-    }
-    if (g->kernel_timing) {  // (the workspace is per stream: no other call records on these events)
-        if (!w->ev0) HIP_TRY(hipEventCreate(w->ev0.put()));
-        if (!w->ev1) HIP_TRY(hipEventCreate(w->ev1.put()));
-        HIP_TRY(hipEventRecord(w->ev0, stream));
-    }
+    PhaseStamps stamps;
+    if ((rc = stamps.begin(a, wgs, s.threads, stream))) return rc;
+    SplitTurn turn;  // split launches in flight per device (SplitSerial)
+    if (split && (rc = turn.wait(dg->device, s, wgs, batch, stream))) return rc;
+    if ((rc = timing_begin(g, w, stream))) return rc;
     if (before_decode) HIP_TRY(hipStreamWaitEvent(stream, before_decode, 0));
-    if (v2) HIP_TRY(launch_decode_v2(a, wgs, lds, stream));
-    else HIP_TRY(launch_decode(g->variant, a, wgs, lds, stream));
-    if (ser) {
-        HIP_TRY(hipEventRecord(ser->ev[ser_slot], stream));
-        ser->shape[ser_slot] = ser_shape;
-        ser->overlap_ok[ser_slot] = ser_ok;
-        ser->last = ser_slot;
-        split_lk.unlock();
-    }
-    if (g->kernel_timing) {
-        HIP_TRY(hipEventRecord(w->ev1, stream));
-        w->ev_recorded = true;
-    }
-#ifdef QL_PHASE_STAMPS
-    {  // diagnostic: per-phase share of wave time, one JSON line on stderr
-        std::vector<uint64_t> h(nst);
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(h.data(), d_st.get(), nst * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        double tot[NUM_STAMPS] = {0}, all = 0;
-        for (size_t i = 0; i < nst; ++i) tot[i % NUM_STAMPS] += (double)h[i];
-        for (int i = 0; i < NUM_STAMPS; ++i) all += tot[i];
-        std::string js = "{\"phase_stamps\": {";
-        for (int i = 0; i < NUM_STAMPS; ++i)
-            js += std::string(i ? ", " : "") + "\"" + STAMP_NAMES[i] + "\": " + std::to_string(all > 0 ? tot[i] / all : 0.);
-        js += "}, \"wave_cycles_total\": " + std::to_string(all) + "}";
-        fprintf(stderr, "%s\n", js.c_str());
-    }
-#endif
-    return QLDPC_OK;
+    if (v2) HIP_TRY(launch_decode_v2(s, a, wgs, stream));
+    else HIP_TRY(launch_decode(s.variant, a, wgs, s.lds_bytes, stream));
+    if (split && (rc = turn.record(stream))) return rc;
+    if ((rc = timing_end(g, w, stream))) return rc;
+    return stamps.report(stream);
 }
 
 const qldpc_rate_plan::Dev *plan_dev(const qldpc_rate_plan *plan, int device) {
@@ -660,12 +707,8 @@ int qldpc::qkd_ldpc_window(qldpc_graph *g, DeviceGraph *dg, const qldpc_rate_pla
             if (r) return r;
             codes = w->codes.get(); palette = w->palette.get(); pal_ok = w->pal_ok.get();
         } else if (!llr) {
-            if ((size_t)batch > w->llr_ws_frames) {
-                HIP_TRY(hipStreamSynchronize(s));
-                w->llr_ws_frames = 0;
-                if (int r = w->llr_ws.alloc((size_t)batch * g->n)) return r;
-                w->llr_ws_frames = (size_t)batch;
-            }
+            if (int r = grow(w->llr_ws_frames, (size_t)batch, s, [&] { return w->llr_ws.alloc((size_t)batch * g->n); }))
+                return r;
             llr = w->llr_ws.get();
         }
     }
@@ -828,23 +871,20 @@ int qldpc_graph_plan(const qldpc_graph *g, int32_t device, int32_t algorithm, in
     DeviceGraph *dg = find_dev(const_cast<qldpc_graph *>(g), device);
     // (a host-only graph answers everything but the device's workgroup count)
     if (!dg && !(g->devs.empty() && !workgroups)) return fail(QLDPC_EINVAL, "graph does not live on that device");
-    const size_t lds = lds_of(*g, algorithm);
+    const LaunchShape s = launch_shape(*g, algorithm, vng_enabled());
     // (split frames: the lanes that run — K parts of split_pl — not the arrays' stride)
-    if (lanes) *lanes = (g->variant == VAR_V2 && g->split_k > 1) ? g->split_k * g->split_pl : g->T;
+    if (lanes) *lanes = s.lanes();
     if (edges_per_lane) *edges_per_lane = g->EPL;
-    if (lds_bytes) *lds_bytes = (int32_t)lds;
-    if (variant)
-        *variant = (g->variant == VAR_V2 && g->split_k > 1) ? "v2_split"
-                   : (g->variant == VAR_V2 && g->v2RG > 0) ? "v2_hybrid" : variant_name(g->variant);
+    if (lds_bytes) *lds_bytes = (int32_t)s.lds_bytes;
+    if (variant) *variant = s.variant_name();
     if (workgroups && g->variant == VAR_FPL) {
         *workgroups = fpl_cn_grid(g->fpl_class_off);  // the check-node pass's grid for one 64-frame tile
     } else if (workgroups) {
         DeviceScope ds;
         if (int rc = ds.enter(dg->device)) return rc;
+        std::lock_guard<std::mutex> lk(dg->mu);
         int b = 0;
-        hipError_t e = g->variant == VAR_V2 ? occupancy_v2(g->v2R, g->v2RG, g->split_k, algorithm, block_threads(*g), lds, &b)
-                                            : occupancy(g->variant, algorithm, g->T, lds, &b);
-        if (e != hipSuccess) return hip_fail(e, "occupancy");
+        if (int rc = blocks_per_cu(dg, s, &b)) return rc;
         *workgroups = b * dg->num_cus;
     }
     return QLDPC_OK;

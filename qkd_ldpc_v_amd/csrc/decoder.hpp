@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 namespace qldpc {
 
 // Per-slot metadata word (slot-major [slot][lane], one uint32 per CSR edge).
@@ -85,7 +87,7 @@ struct DecodeArgs {
     // decoder parameters
     int alg, max_it, thr_on;
     double thr, primary, secondary;
-    // SPA edge-form constants, computed by the host C library (capi.hip decode_on):
+    // SPA edge-form constants, computed by the host C library (capi.hip fill_args):
     double spa_tlim;  // tanh(min(thr, 44) / 2.)  (1 when clipping is off)
     double spa_ctop;  // 2. * atanh(1 - 2^-53)
     // frames
@@ -245,19 +247,60 @@ hipError_t launch_build_frames(int n, int m, int max_dc, const int32_t *ell_col,
                                double *llr, uint8_t *synd, uint8_t *codes, double *palette, uint8_t *pal_ok,
                                const int32_t *col_orig, hipStream_t stream);
 
-// LDS bytes of a V2 launch; R/RG select the shape (whether message slots live in LDS).
-// rows_lds: min-sum row aggregates kept in LDS on the hybrid shape (-1: all m).
-size_t lds_bytes_v2(int alg, int n, int m, int T, bool split = false, int R = 0, int RG = 0, int rows_lds = -1,
-                    int gcb = 0);
+// One decode launch, decided once per call from the graph, the algorithm and
+// the launch-time knobs (plan.hip launch_shape): which kernel runs, with how
+// many threads and how much dynamic LDS.  Host only; every consumer (the
+// occupancy query, the argument fill, the launch, qldpc_graph_plan) reads the
+// choice from here and derives nothing of it again.
+struct LaunchShape {
+    int variant = 0, alg = 0;
+    int threads = 0;       // per workgroup
+    size_t lds_bytes = 0;  // dynamic LDS per workgroup
+    // V2: the template arguments of decode_v2_kernel (decoder_v2.hip kernel_of)
+    int R = 0, RG = 0, RL = 0;     // message slots per lane in VGPRs / global scratch / LDS
+    int split_k = 1;               // workgroups per frame (1: not split)
+    int part_lanes = REG_TSTRIDE;  // PL: a split part's lanes
+    bool vng = false;              // min-sum bit gather (DecodeArgs::vn_rows)
+    bool rglb = false;             // min-sum row aggregates (partly) in global scratch
+    int rows_lds = 0;              // rows whose aggregates the LDS image holds
+    int gcb = 0;                   // split exchange gather: bits per LDS chunk
+    int lanes() const { return split_k * threads; }  // the lanes that run per frame
+    // What the occupancy query asks (V2): the plain instantiation of the same
+    // (R, RG, split, part lanes) at this launch's threads and LDS bytes, without
+    // LDS message slots or the bit gather.  NOT the launched kernel whenever RL > 0
+    // or vng: the workgroup counts of those launches come from this stand-in.
+    LaunchShape occupancy_proxy() const {
+        LaunchShape p = *this;
+        p.RL = 0;
+        p.vng = p.rglb = false;
+        return p;
+    }
+    const char *variant_name() const;  // qldpc_graph_plan's: reg_lds .. v2, v2_hybrid, v2_split, fpl
+    std::string name() const;          // e.g. v2<alg=0,R=40,RG=0,RL=5,split=1,pl=1024,vng=0,rglb=0>
+};
+
+// The V2 shape of a scalar description: RL and lds_bytes by the V2Layout fit tests
+// (decoder_v2.hip; also the planners' fit queries, which read .lds_bytes / .RL).
+struct V2ShapeQuery {
+    int alg = 0, n = 0;
+    int rows = 0;          // m, or the rows of a split frame's largest part
+    int threads = 0;       // the workgroup's (split: one part's) lanes
+    int split_k = 1;
+    int R = 0, RG = 0;     // (split frames: every plan's slots share one LDS image)
+    int rows_lds = -1;     // min-sum row aggregates kept in LDS on the hybrid shape (-1: all)
+    int gcb = 0;
+    bool want_vng = false, rglb = false;
+};
+LaunchShape v2_launch_shape(const V2ShapeQuery &q);
 // Whether a V2 shape can run the min-sum bit gather (DecodeArgs::vn_rows):
 // the dv <= 4 register shape, or the hybrid shape when the padded edge
 // positions' two code bits fit the LDS byte area.
 bool v2_vng_ok(int alg, int R, int RG, int split_k, int dv_max, int m);
-// Split frames: whether the SPA layout keeps its LDS message slots at gcb exchange-gather bits.
-bool v2_split_rl_fits(int n, int mrows, int gcb, int pl);
 constexpr int V2_VNG_DUMMY_CHUNKS = 64;  // hybrid: one scratch code byte per lane for dummy slots
-hipError_t launch_decode_v2(const DecodeArgs &a, int workgroups, size_t lds_bytes, hipStream_t stream);
-hipError_t occupancy_v2(int R, int RG, int split_k, int alg, int T, size_t lds_bytes, int *blocks_per_cu);
+// hipErrorInvalidValue: the shape has no instantiation, or the arguments lack what it reads.
+hipError_t launch_decode_v2(const LaunchShape &s, const DecodeArgs &a, int workgroups, hipStream_t stream);
+// Max resident workgroups per CU of the shape's kernel (callers pass occupancy_proxy()).
+hipError_t occupancy_v2(const LaunchShape &s, int *blocks_per_cu);
 hipError_t launch_palettize(int n, int nc, int batch, const double *llr, uint8_t *codes, double *palette,
                             uint8_t *pal_ok, const int32_t *col_orig, hipStream_t stream);
 // Trial generator workspace (uint32 words) of `batch` trials.

@@ -1540,79 +1540,89 @@ __global__ void __launch_bounds__(256) palettize_kernel(int n, int nc, const dou
 
 using KernelFn = void (*)(DecodeArgs);
 
-template <int R, int RG, bool SPLIT = false, int PL = REG_TSTRIDE>
-KernelFn pick_v2(int alg) {
-    switch (alg) {
-    case 0: return decode_v2_kernel<0, R, RG, SPLIT, 0, false, false, PL>;
-    case 1: return decode_v2_kernel<1, R, RG, SPLIT, 0, false, false, PL>;
-    case 2: return decode_v2_kernel<2, R, RG, SPLIT, 0, false, false, PL>;
-    case 3: return decode_v2_kernel<3, R, RG, SPLIT, 0, false, false, PL>;
-    case 4: return decode_v2_kernel<4, R, RG, SPLIT, 0, false, false, PL>;
-    default: return decode_v2_kernel<5, R, RG, SPLIT, 0, false, false, PL>;
-    }
-}
+// The template arguments of one instantiation family (every algorithm it is built for).
+template <int R_, int RG_, bool SPLIT_, int RL_, bool VNG_, bool RGLB_, int PL_>
+struct Inst {
+    static constexpr int R = R_, RG = RG_, RL = RL_, PL = PL_;
+    static constexpr bool SPLIT = SPLIT_, VNG = VNG_, RGLB = RGLB_;
+};
 
-KernelFn kernel_v2_vng(int alg, int RG, bool rglb) {
-    if (RG > 0 && rglb) {
-        switch (alg) {
-        case 2: return decode_v2_kernel<2, V2_R_SMALL, V2_RG_HYBRID, false, 0, true, true>;
-        case 3: return decode_v2_kernel<3, V2_R_SMALL, V2_RG_HYBRID, false, 0, true, true>;
-        case 4: return decode_v2_kernel<4, V2_R_SMALL, V2_RG_HYBRID, false, 0, true, true>;
-        default: return decode_v2_kernel<5, V2_R_SMALL, V2_RG_HYBRID, false, 0, true, true>;
+// Every decode_v2_kernel instantiation the library builds, and the only place
+// that names one: a new instantiation is a new row.  nullptr: no such kernel.
+// The LDS-slot instantiations (RL > 0) exist for the SPA family only, the bit
+// gather's (VNG) for the min-sum family only.
+KernelFn kernel_of(const LaunchShape &s) {
+    constexpr int T = REG_TSTRIDE, H = REG_TSTRIDE / 2, SG = V2_RG_SPLIT;
+    KernelFn k = nullptr;
+    const auto is = [&](auto inst) {  // the row is the shape's: take its kernel of s.alg
+        using I = decltype(inst);
+        if (s.R != I::R || s.RG != I::RG || (s.split_k > 1) != I::SPLIT || s.RL != I::RL || s.vng != I::VNG ||
+            s.rglb != I::RGLB || s.part_lanes != I::PL)
+            return false;
+        if constexpr (!I::VNG) {
+            if (s.alg == 0) k = decode_v2_kernel<0, I::R, I::RG, I::SPLIT, I::RL, I::VNG, I::RGLB, I::PL>;
+            if (s.alg == 1) k = decode_v2_kernel<1, I::R, I::RG, I::SPLIT, I::RL, I::VNG, I::RGLB, I::PL>;
         }
-    }
-    if (RG > 0) {
-        switch (alg) {
-        case 2: return decode_v2_kernel<2, V2_R_SMALL, V2_RG_HYBRID, false, 0, true>;
-        case 3: return decode_v2_kernel<3, V2_R_SMALL, V2_RG_HYBRID, false, 0, true>;
-        case 4: return decode_v2_kernel<4, V2_R_SMALL, V2_RG_HYBRID, false, 0, true>;
-        default: return decode_v2_kernel<5, V2_R_SMALL, V2_RG_HYBRID, false, 0, true>;
+        if constexpr (I::RL == 0) {
+            if (s.alg == 2) k = decode_v2_kernel<2, I::R, I::RG, I::SPLIT, I::RL, I::VNG, I::RGLB, I::PL>;
+            if (s.alg == 3) k = decode_v2_kernel<3, I::R, I::RG, I::SPLIT, I::RL, I::VNG, I::RGLB, I::PL>;
+            if (s.alg == 4) k = decode_v2_kernel<4, I::R, I::RG, I::SPLIT, I::RL, I::VNG, I::RGLB, I::PL>;
+            if (s.alg == 5) k = decode_v2_kernel<5, I::R, I::RG, I::SPLIT, I::RL, I::VNG, I::RGLB, I::PL>;
         }
-    }
-    switch (alg) {
-    case 2: return decode_v2_kernel<2, V2_R_TIGHT, 0, false, 0, true>;
-    case 3: return decode_v2_kernel<3, V2_R_TIGHT, 0, false, 0, true>;
-    case 4: return decode_v2_kernel<4, V2_R_TIGHT, 0, false, 0, true>;
-    default: return decode_v2_kernel<5, V2_R_TIGHT, 0, false, 0, true>;
-    }
-}
-
-// Split frames: parts of 16 or 8 waves (PL lanes), SG scratch slots (0 or V2_RG_SPLIT).
-template <int SG, int PL>
-KernelFn kernel_split(int alg, bool rl) {
-    constexpr int RL = v2_rl_split(PL);
-    if (rl) return alg == 0 ? decode_v2_kernel<0, V2_R_SPLIT, SG, true, RL, false, false, PL>
-                            : decode_v2_kernel<1, V2_R_SPLIT, SG, true, RL, false, false, PL>;
-    return pick_v2<V2_R_SPLIT, SG, true, PL>(alg);
-}
-
-KernelFn kernel_v2(int R, int RG, int split_k, int alg, bool rl, int pl = REG_TSTRIDE) {
-    if (split_k > 1) {
-        if (RG != 0 && RG != V2_RG_SPLIT) return nullptr;  // (no such instantiation)
-        if (pl == REG_TSTRIDE / 2)
-            return RG ? kernel_split<V2_RG_SPLIT, REG_TSTRIDE / 2>(alg, rl) : kernel_split<0, REG_TSTRIDE / 2>(alg, rl);
-        return RG ? kernel_split<V2_RG_SPLIT, REG_TSTRIDE>(alg, rl) : kernel_split<0, REG_TSTRIDE>(alg, rl);
-    }
-    if (rl) return alg == 0 ? decode_v2_kernel<0, V2_R_TIGHT, 0, false, V2_RL> : decode_v2_kernel<1, V2_R_TIGHT, 0, false, V2_RL>;
-    if (RG > 0) return pick_v2<V2_R_SMALL, V2_RG_HYBRID>(alg);
-    if (R == V2_R_TIGHT) return pick_v2<V2_R_TIGHT, 0>(alg);
-    if (R == V2_R_SMALL) return pick_v2<V2_R_SMALL, 0>(alg);
-    return pick_v2<V2_R_MID, 0>(alg);
+        return true;
+    };
+    (void)(  // one workgroup per frame: the register shapes and the hybrid shape, all six algorithms
+        is(Inst<V2_R_TIGHT, 0, false, 0, false, false, T>{}) ||
+        is(Inst<V2_R_SMALL, 0, false, 0, false, false, T>{}) ||
+        is(Inst<V2_R_MID, 0, false, 0, false, false, T>{}) ||
+        is(Inst<V2_R_SMALL, V2_RG_HYBRID, false, 0, false, false, T>{}) ||
+        // ... SPA family with V2_RL message slots in LDS
+        is(Inst<V2_R_TIGHT, 0, false, V2_RL, false, false, T>{}) ||
+        // ... min-sum family with the bit gather; hybrid: rows in LDS or partly in global scratch
+        is(Inst<V2_R_TIGHT, 0, false, 0, true, false, T>{}) ||
+        is(Inst<V2_R_SMALL, V2_RG_HYBRID, false, 0, true, false, T>{}) ||
+        is(Inst<V2_R_SMALL, V2_RG_HYBRID, false, 0, true, true, T>{}) ||
+        // split frames: parts of 16 or 8 waves, without or with scratch slots
+        is(Inst<V2_R_SPLIT, 0, true, 0, false, false, T>{}) ||
+        is(Inst<V2_R_SPLIT, SG, true, 0, false, false, T>{}) ||
+        is(Inst<V2_R_SPLIT, 0, true, 0, false, false, H>{}) ||
+        is(Inst<V2_R_SPLIT, SG, true, 0, false, false, H>{}) ||
+        // ... SPA family with v2_rl_split(PL) message slots in LDS
+        is(Inst<V2_R_SPLIT, 0, true, v2_rl_split(T), false, false, T>{}) ||
+        is(Inst<V2_R_SPLIT, SG, true, v2_rl_split(T), false, false, T>{}) ||
+        is(Inst<V2_R_SPLIT, 0, true, v2_rl_split(H), false, false, H>{}) ||
+        is(Inst<V2_R_SPLIT, SG, true, v2_rl_split(H), false, false, H>{}));
+    return k;
 }
 
 }  // namespace
 
-size_t lds_bytes_v2(int alg, int n, int m, int T, bool split, int R, int RG, int rows_lds, int gcb) {
-    if (split)  // (T: the part's lanes)
-        return V2Layout(n, m, (n + 3) / 4, T, alg >= 2, true, v2_use_rl_split(alg, n, m, gcb, T) ? v2_rl_split(T) : 0,
-                        false, gcb, T)
-            .bytes;
-    const bool rl = v2_use_rl(alg, R, RG, split, n, m, T);
-    return V2Layout(n, rows_lds >= 0 ? rows_lds : m, (n + 3) / 4, T, alg >= 2, split, rl ? V2_RL : 0,
-                    V2_ROWSCAN_ON && !split && RG == 0).bytes;
+// The only calls of the V2Layout fit tests: whether the SPA family keeps message
+// slots in LDS (RL), and the bytes of the image the kernel will lay out.
+LaunchShape v2_launch_shape(const V2ShapeQuery &q) {
+    const bool split = q.split_k > 1, minsum = q.alg >= 2;
+    LaunchShape s;
+    s.variant = VAR_V2;
+    s.alg = q.alg;
+    s.threads = q.threads;
+    s.R = q.R;
+    s.RG = q.RG;
+    s.split_k = q.split_k;
+    s.vng = q.want_vng;
+    s.rglb = q.rglb;
+    s.rows_lds = q.rows_lds >= 0 ? q.rows_lds : q.rows;
+    if (split) {
+        s.part_lanes = q.threads;
+        s.gcb = q.gcb;
+        s.RL = v2_use_rl_split(q.alg, q.n, q.rows, q.gcb, q.threads) ? v2_rl_split(q.threads) : 0;
+        s.lds_bytes = V2Layout(q.n, q.rows, (q.n + 3) / 4, q.threads, minsum, true, s.RL, false, q.gcb, q.threads).bytes;
+    } else {
+        s.RL = v2_use_rl(q.alg, q.R, q.RG, false, q.n, q.rows, q.threads) ? V2_RL : 0;
+        s.lds_bytes = V2Layout(q.n, s.rows_lds, (q.n + 3) / 4, q.threads, minsum, false, s.RL,
+                               V2_ROWSCAN_ON && q.RG == 0).bytes;
+    }
+    return s;
 }
-
-bool v2_split_rl_fits(int n, int mrows, int gcb, int pl) { return v2_use_rl_split(0, n, mrows, gcb, pl); }
 
 bool v2_vng_ok(int alg, int R, int RG, int split_k, int dv_max, int m) {
     if (alg < 2 || split_k > 1 || m >= 0xFFFF) return false;
@@ -1626,32 +1636,30 @@ bool v2_vng_ok(int alg, int R, int RG, int split_k, int dv_max, int m) {
 static_assert(V2_R_TIGHT <= 63 && V2_R_SMALL <= 63 && V2_R_MID <= 63,
               "register shapes without RG slots must have <= 63 slots (row_sem / row_rmask)");
 
-hipError_t launch_decode_v2(const DecodeArgs &a, int workgroups, size_t lds_bytes, hipStream_t stream) {
+hipError_t launch_decode_v2(const LaunchShape &s, const DecodeArgs &a, int workgroups, hipStream_t stream) {
+    const bool split = s.split_k > 1;
+    // the arguments are the shape's: lanes, parts, and the tables each choice reads
+    if (a.T != s.threads || a.split_k != s.split_k || a.alg != s.alg) return hipErrorInvalidValue;
+    if (s.vng != (a.vn_rows != nullptr) || s.rglb != (a.rows_wg_offset >= 0)) return hipErrorInvalidValue;
     // the scan of one-workgroup register frames reads the row structure masks
     // (plan_v2 only builds register shapes of <= 63 slots, which always get row_sem)
-    if (a.split_k <= 1 && a.v2RG == 0 && !a.row_sem) return hipErrorInvalidValue;
-    if (a.split_k <= 1 && a.n >= 0xFFFF) return hipErrorInvalidValue;  // col_off8: LDS totals, bit ids < 2^16
-    if (a.vn_rows && !v2_vng_ok(a.alg, a.v2R, a.v2RG, a.split_k, a.dv_max, a.m)) return hipErrorInvalidValue;
-    if (a.rows_wg_offset >= 0 && !(a.vn_rows && a.v2RG > 0)) return hipErrorInvalidValue;
-    KernelFn k = a.vn_rows ? kernel_v2_vng(a.alg, a.v2RG, a.rows_wg_offset >= 0)
-                           : kernel_v2(a.v2R, a.v2RG, a.split_k, a.alg,
-                                       a.split_k > 1 ? v2_use_rl_split(a.alg, a.n, a.split_mrows, a.split_cb, a.T)
-                                                     : v2_use_rl(a.alg, a.v2R, a.v2RG, false, a.n, a.m, a.T),
-                                       a.split_k > 1 ? a.T : REG_TSTRIDE);
+    if (!split && s.RG == 0 && !a.row_sem) return hipErrorInvalidValue;
+    if (!split && a.n >= 0xFFFF) return hipErrorInvalidValue;  // col_off8: LDS totals, bit ids < 2^16
+    if (s.vng && !v2_vng_ok(s.alg, s.R, s.RG, s.split_k, a.dv_max, a.m)) return hipErrorInvalidValue;
+    KernelFn k = kernel_of(s);
     if (!k) return hipErrorInvalidValue;
-    if (a.split_k > 1 && a.T != REG_TSTRIDE && a.T != REG_TSTRIDE / 2) return hipErrorInvalidValue;
-    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(k), lds_bytes);
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(k), s.lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(workgroups), dim3(a.T), lds_bytes, stream, a);
+    hipLaunchKernelGGL(k, dim3(workgroups), dim3(s.threads), s.lds_bytes, stream, a);
     return hipGetLastError();
 }
 
-hipError_t occupancy_v2(int R, int RG, int split_k, int alg, int T, size_t lds_bytes, int *blocks_per_cu) {
-    KernelFn k = kernel_v2(R, RG, split_k, alg, false, split_k > 1 ? T : REG_TSTRIDE);
+hipError_t occupancy_v2(const LaunchShape &s, int *blocks_per_cu) {
+    KernelFn k = kernel_of(s);
     if (!k) return hipErrorInvalidValue;
-    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(k), lds_bytes);
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(k), s.lds_bytes);
     if (e != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, T, lds_bytes);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, s.threads, s.lds_bytes);
 }
 
 hipError_t launch_palettize(int n, int nc, int batch, const double *llr, uint8_t *codes, double *palette,

@@ -303,6 +303,11 @@ int env_int(const char *name, int dflt);  // a QLDPC_* knob under the diagnostic
 void plan(qldpc_graph &g);
 bool plan_v2(qldpc_graph &g, const int32_t *row_ptr);
 bool plan_v2_split(qldpc_graph &g, const int32_t *row_ptr, const int32_t *col_idx);
+// ... and what a decode of the planned graph launches (every variant; V2 through
+// decoder_v2.hip's v2_launch_shape).  vng_enabled: the QLDPC_VNG knob, as vng_enabled() reads it.
+bool vng_enabled();
+LaunchShape launch_shape(const qldpc_graph &g, int alg, bool vng_enabled);
+void print_launch_shapes(const qldpc_graph &g);  // the {"launch": ...} lines of QLDPC_DEBUG_PLAN
 
 // layout.hip — validate, plan, build every table; touches no device.  layout:
 // QLDPC_LAYOUT_AUTO (the planner's choice) or QLDPC_LAYOUT_FRAME_PER_LANE.

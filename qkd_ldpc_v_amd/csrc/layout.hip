@@ -772,6 +772,7 @@ int build_layout(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *co
     g->E = E;
     Layout L{n, m, row_ptr, col_idx, col_ptr, row_idx, E, g.get(), t, layout};
     if (int rc = L.build()) return rc;
+    if (qldpc_diag_env("QLDPC_DEBUG_PLAN")) print_launch_shapes(*g);  // (every variant, after its plan / layout lines)
     out = std::move(g);
     return QLDPC_OK;
 }

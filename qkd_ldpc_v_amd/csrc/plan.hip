@@ -3,6 +3,7 @@
 // Host arithmetic only; layout.hip builds the tables of the plan chosen here.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -187,11 +188,13 @@ bool plan_v2(qldpc_graph &g, const int32_t *row_ptr) {
         bool rows_global = false;
         // (the shape's own layout: the mask-driven scan's syndrome words exist
         // on the register shapes only)
-        if (lds_bytes_v2(2, g.n, g.m, W * 64, false, sh[0], sh[1]) > LDS_LIMIT) {
-            if (sh[1] == 0 || !g.vng_h_fit || g.m >= 0xFFFF ||
-                lds_bytes_v2(0, g.n, g.m, W * 64, false, sh[0], sh[1]) > LDS_LIMIT ||
-                lds_bytes_v2(2, g.n, g.m, W * 64, false, sh[0], sh[1], 0) > LDS_LIMIT)
-                continue;
+        const auto lds = [&](int alg, int rows_lds = -1) {
+            V2ShapeQuery q;
+            q.alg = alg, q.n = g.n, q.rows = g.m, q.threads = W * 64, q.R = sh[0], q.RG = sh[1], q.rows_lds = rows_lds;
+            return v2_launch_shape(q).lds_bytes;
+        };
+        if (lds(2) > LDS_LIMIT) {
+            if (sh[1] == 0 || !g.vng_h_fit || g.m >= 0xFFFF || lds(0) > LDS_LIMIT || lds(2, 0) > LDS_LIMIT) continue;
             rows_global = true;
         }
         const long long cap = 64LL * std::max<long long>((E + 64LL * W - 1) / (64LL * W), g.max_dc);
@@ -217,7 +220,7 @@ bool plan_v2(qldpc_graph &g, const int32_t *row_ptr) {
                     nrp[jr + 1] = nrp[jr] + (row_ptr[order[jr] + 1] - row_ptr[order[jr]]);
                 if (!rows_global) break;
                 int wn = env_int("QLDPC_ROWS_LDS", 1) ? W : 0;
-                while (wn > 0 && lds_bytes_v2(2, g.n, g.m, W * 64, false, sh[0], sh[1], rb[wn]) > LDS_LIMIT) --wn;
+                while (wn > 0 && lds(2, rb[wn]) > LDS_LIMIT) --wn;
                 const bool agree = share == 1.0 || (pass > 0 && wn == wl);
                 wl = wn;
                 if (agree) break;
@@ -309,9 +312,12 @@ bool plan_v2_split(qldpc_graph &g, const int32_t *row_ptr, const int32_t *col_id
         int mrows = 0;
         for (int r = 0; r <= K; ++r) prow[r] = rb[std::min(W, r * WP)];
         for (int r = 0; r < K; ++r) mrows = std::max(mrows, prow[r + 1] - prow[r]);
-        if (lds_bytes_v2(2, g.n, mrows, PL, true, 0, 0, -1, 0) > LIM ||
-            lds_bytes_v2(0, g.n, mrows, PL, true, 0, 0, -1, 0) > LIM)
-            return false;
+        const auto part = [&](int alg, int gcb) {  // a part's shape at gcb exchange-gather bits
+            V2ShapeQuery q;
+            q.alg = alg, q.n = g.n, q.rows = mrows, q.threads = PL, q.split_k = K, q.R = V2_R_SPLIT, q.RG = RG, q.gcb = gcb;
+            return v2_launch_shape(q);
+        };
+        if (part(2, 0).lds_bytes > LIM || part(0, 0).lds_bytes > LIM) return false;
         // Exchange gather (DecodeArgs::xoff): the largest LDS chunk of a part's
         // bits every algorithm's layout holds (SPA keeps its LDS message slots
         // when they fit without it), split evenly; QLDPC_SPLIT_X=0: the
@@ -319,11 +325,10 @@ bool plan_v2_split(qldpc_graph &g, const int32_t *row_ptr, const int32_t *col_id
         int cb = 0, nc = 0;
         if (env_int("QLDPC_SPLIT_X", 1)) {
             const int own = (g.n + K - 1) / K;
-            const bool rl0 = v2_split_rl_fits(g.n, mrows, 0, PL);
+            const bool rl0 = part(0, 0).RL > 0;
             auto fits = [&](int c) {
-                return lds_bytes_v2(2, g.n, mrows, PL, true, 0, 0, -1, c) <= LIM &&
-                       lds_bytes_v2(0, g.n, mrows, PL, true, 0, 0, -1, c) <= LIM &&
-                       (!rl0 || v2_split_rl_fits(g.n, mrows, c, PL));
+                const LaunchShape spa = part(0, c);
+                return part(2, c).lds_bytes <= LIM && spa.lds_bytes <= LIM && (!rl0 || spa.RL > 0);
             };
             int lo = 0, hi = std::min(own, 0xFFFF);
             while (lo < hi) {
@@ -404,6 +409,67 @@ bool plan_v2_split(qldpc_graph &g, const int32_t *row_ptr, const int32_t *col_id
     const Plan pick = (ps.K && (!p0.K || 3 * ps.f >= 4 * p0.f)) ? ps : p0;
     if (!pick.K) return false;
     return attempt(pick.K, pick.RG, pick.WR);  // (the last attempt sets the plan)
+}
+
+// QLDPC_VNG=0 (diagnostic switch, read at every launch): VN phases instead of the min-sum bit gather.
+bool vng_enabled() {
+    const char *e = qldpc_diag_env("QLDPC_VNG");
+    return !(e && std::strcmp(e, "0") == 0);
+}
+
+// The launch of (graph, algorithm): a few integer operations, computed per call
+// so that a knob flipped between two decodes of one graph is honoured.
+LaunchShape launch_shape(const qldpc_graph &g, int alg, bool vng_enabled) {
+    if (g.variant == VAR_V2) {
+        const bool split = g.split_k > 1;
+        V2ShapeQuery q;
+        q.alg = alg, q.n = g.n, q.R = g.v2R, q.RG = g.v2RG, q.split_k = g.split_k;
+        q.rows = split ? g.split_mrows : g.m;
+        q.threads = split ? g.split_pl : g.T;  // one part's lanes, or the graph's
+        q.gcb = g.split_cb;
+        q.rglb = g.rows_global_ms && alg >= 2;
+        if (q.rglb) q.rows_lds = g.rows_lds_ms;
+        q.want_vng = g.vng && vng_enabled && v2_vng_ok(alg, g.v2R, g.v2RG, g.split_k, g.dv_max, g.m);
+        return v2_launch_shape(q);
+    }
+    LaunchShape s;
+    s.variant = g.variant;
+    s.alg = alg;
+    s.threads = g.T;  // (frame-per-lane: FPL_LANES; its transposes' LDS is static)
+    s.lds_bytes = g.variant == VAR_FPL ? 0 : lds_bytes_for(g.variant, g.n, g.m, g.T);
+    return s;
+}
+
+const char *LaunchShape::variant_name() const {
+    switch (variant) {
+    case VAR_REG_LDS: return "reg_lds";
+    case VAR_GLB_LDS: return "glb_lds";
+    case VAR_V2: return split_k > 1 ? "v2_split" : RG > 0 ? "v2_hybrid" : "v2";
+    case VAR_FPL: return "fpl";
+    default: return "glb_glb";
+    }
+}
+
+std::string LaunchShape::name() const {
+    char b[128];
+    if (variant == VAR_V2)
+        snprintf(b, sizeof b, "v2<alg=%d,R=%d,RG=%d,RL=%d,split=%d,pl=%d,vng=%d,rglb=%d>", alg, R, RG, RL, split_k,
+                 part_lanes, (int)vng, (int)rglb);
+    else snprintf(b, sizeof b, "%s<alg=%d,T=%d>", variant_name(), alg, threads);
+    return b;
+}
+
+// One {"launch": ...} line per algorithm on stderr (QLDPC_DEBUG_PLAN): what a
+// decode of this graph would launch under the knobs as they are now.
+void print_launch_shapes(const qldpc_graph &g) {
+    for (int alg = 0; alg <= 5; ++alg) {
+        const LaunchShape s = launch_shape(g, alg, vng_enabled());
+        fprintf(stderr, "{\"launch\": {\"alg\": %d, \"variant\": \"%s\", \"name\": \"%s\", \"threads\": %d, "
+                        "\"lanes\": %d, \"lds_bytes\": %zu, \"R\": %d, \"RG\": %d, \"RL\": %d, \"split_k\": %d, "
+                        "\"part_lanes\": %d, \"vng\": %d, \"rglb\": %d, \"rows_lds\": %d, \"gcb\": %d}}\n",
+                alg, s.variant_name(), s.name().c_str(), s.threads, s.lanes(), s.lds_bytes, s.R, s.RG, s.RL, s.split_k,
+                s.part_lanes, (int)s.vng, (int)s.rglb, s.rows_lds, s.gcb);
+    }
 }
 
 }  // namespace qldpc
