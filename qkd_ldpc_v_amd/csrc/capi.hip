@@ -42,34 +42,17 @@ int hip_fail(hipError_t e, const char *what) {
 
 namespace {
 
-// The graph's tables on the current device.  (pair_* and the label tables stay
-// NULL on graphs without them: the launches test the pointers.)
+// The graph's tables on the current device: every entry of QLDPC_GRAPH_TABLES
+// whose `when` holds for this graph, in the list's order; the first error ends
+// it.  (The others stay NULL: the launches test the pointers.)
 int upload_tables(DeviceGraph &dg, const qldpc_graph &g, const GraphTables &t) {
+    static_assert(T_ALWAYS == 0 && T_FPL == 1 && T_PAIRED == 2 && T_RELABELLED == 3, "exists[] is indexed by TableWhen");
+    const bool exists[T_WHEN_COUNT] = {true, g.variant == VAR_FPL, g.paired, t.relabelled()};
     int rc;
-    if ((rc = dg.slot_meta.upload(t.slot_meta)) || (rc = dg.slot_meta_ms.upload(t.slot_meta_ms)) ||
-        (rc = dg.vn_mask.upload(t.vn_mask)) || (rc = dg.vn_mask_ms.upload(t.vn_mask_ms)) ||
-        (rc = dg.vn_exec.upload(t.vn_exec)) || (rc = dg.vn_exec_ms.upload(t.vn_exec_ms)) ||
-        (rc = dg.slot_meta2.upload(t.slot_meta2)) || (rc = dg.slot_meta2_ms.upload(t.slot_meta2_ms)) ||
-        (rc = dg.hd_bits.upload(t.hd_bits)) || (rc = dg.hd_dv.upload(t.hd_dv)) ||
-        (rc = dg.stage_off.upload(t.stage_off)) || (rc = dg.row_orig.upload(t.row_orig)) ||
-        (rc = dg.part_row0.upload(t.part_row0)) || (rc = dg.xoff.upload(t.xoff)) ||
-        (rc = dg.xbit.upload(t.xbit)) || (rc = dg.xbit_ms.upload(t.xbit_ms)) ||
-        (rc = dg.lane_row0.upload(t.lane_row0)) || (rc = dg.wave_rows.upload(t.wave_rows)) ||
-        (rc = dg.lane_head.upload(t.lane_head)) || (rc = dg.lane_nst.upload(t.lane_nst)) ||
-        (rc = dg.lane_epl.upload(t.lane_epl)) || (rc = dg.ell_col.upload(t.ell_col)) ||
-        (rc = dg.row_deg.upload(t.row_deg)) || (rc = dg.iso_bits.upload(t.iso_bits)) ||
-        (rc = dg.vn_rows.upload(t.vn_rows)) || (rc = dg.vng_bits.upload(t.vng_bits)) ||
-        (rc = dg.vng_meta2.upload(t.vng_meta2)) || (rc = dg.row_sem.upload(t.row_sem)) ||
-        (rc = dg.vng_rec.upload(t.vng_rec)) ||
-        (rc = dg.row_rmask.upload(t.row_rmask)) ||
-        (g.variant == VAR_FPL &&
-         ((rc = dg.fpl_row_ptr.upload(t.fpl_row_ptr)) || (rc = dg.fpl_col.upload(t.fpl_col)) ||
-          (rc = dg.fpl_cslot.upload(t.fpl_cslot)) || (rc = dg.fpl_col_ptr.upload(t.fpl_col_ptr)) ||
-          (rc = dg.fpl_rows.upload(t.fpl_rows)))) ||
-        (g.paired && ((rc = dg.pair_src.upload(t.pair_src)) || (rc = dg.pair_col.upload(t.pair_col)))) ||
-        (!t.col_orig.empty() && ((rc = dg.col_orig.upload(t.col_orig)) || (rc = dg.col_lab.upload(t.col_lab)) ||
-                                 (rc = dg.ell_lab.upload(t.ell_lab)))))
-        return rc;
+#define QLDPC_X(type, name, when, digested) \
+    if (exists[when] && (rc = dg.name.upload(t.name))) return rc;
+    QLDPC_GRAPH_TABLES(QLDPC_X)
+#undef QLDPC_X
     return QLDPC_OK;
 }
 

@@ -194,33 +194,49 @@ struct TrialSlot {
     qldpc_trials_job *owner = nullptr;  // the job whose results it holds
 };
 
+// ---- the graph's index tables ---------------------------------------------------
+// Every table layout.hip builds from H, once: X(element type, name, when it
+// exists on a device, whether layout_digest hashes it).  GraphTables (the host
+// vectors), DeviceGraph's table members, upload_tables (capi.hip) and
+// layout_digest (layout.hip) are generated from this list, in this order (line
+// by line, left to right): the upload's, and the digest's that
+// tests/test_layout.py pins.  A table that does not exist on a device stays a
+// NULL pointer there, which the launches test; a T_ALWAYS table is allocated
+// even when it is empty.  T_FPL: frame-per-lane graphs (VAR_FPL); T_PAIRED:
+// g.paired, the v1 occurrence pairing of an unsorted adjacency; T_RELABELLED:
+// V2 bank relabelling (col_orig non-empty).
+enum TableWhen { T_ALWAYS, T_FPL, T_PAIRED, T_RELABELLED, T_WHEN_COUNT };
+#define QLDPC_GRAPH_TABLES(X)                                                                                          \
+    X(uint32_t, slot_meta, T_ALWAYS, true) X(uint32_t, slot_meta_ms, T_ALWAYS, true) /* _ms: min-sum, rows by kpos */  \
+    X(uint64_t, vn_mask, T_ALWAYS, true) X(uint64_t, vn_mask_ms, T_ALWAYS, true) /* V2: [wave][dv_max] slot masks */   \
+    X(uint64_t, vn_exec, T_ALWAYS, true) X(uint64_t, vn_exec_ms, T_ALWAYS, true) /* V2: [wave][dv_max][slot] lanes */  \
+    X(uint32_t, slot_meta2, T_ALWAYS, true) X(uint32_t, slot_meta2_ms, T_ALWAYS, true) /* hybrid: slot's stage pos */   \
+    X(int32_t, hd_bits, T_ALWAYS, true) X(int32_t, hd_dv, T_ALWAYS, true) X(int32_t, stage_off, T_ALWAYS, true)        \
+    X(int32_t, row_orig, T_ALWAYS, true)  /* V2: layout row -> original row (syndrome index) */                        \
+    X(int32_t, part_row0, T_ALWAYS, true) /* V2 split: first layout row of each part */                                \
+    X(int32_t, xoff, T_ALWAYS, true)      /* V2 split exchange: region starts */                                       \
+    X(uint16_t, xbit, T_ALWAYS, true) X(uint16_t, xbit_ms, T_ALWAYS, true) /* ... stage position's chunk-local bit */  \
+    X(int32_t, lane_row0, T_ALWAYS, true) X(int32_t, wave_rows, T_ALWAYS, true) X(int32_t, lane_head, T_ALWAYS, true)  \
+    X(int32_t, lane_nst, T_ALWAYS, true) X(int32_t, lane_epl, T_ALWAYS, true) X(int32_t, ell_col, T_ALWAYS, true)      \
+    X(int32_t, row_deg, T_ALWAYS, true) X(int32_t, iso_bits, T_ALWAYS, true)                                           \
+    X(uint32_t, vn_rows, T_ALWAYS, true) /* V2 min-sum bit gather: [n or chunks][2] four u16 layout rows */            \
+    X(uint32_t, vng_bits, T_ALWAYS, true) X(uint32_t, vng_meta2, T_ALWAYS, true) /* hybrid bit gather: order, slots */ \
+    X(uint64_t, row_sem, T_ALWAYS, true)   /* V2 scan: [wave][slot][4] START / END / PARK lane masks (+ pad) */        \
+    X(uint32_t, vng_rec, T_ALWAYS, true)   /* register-shape bit gather: per slot, byte offset | shift << 16 */        \
+    X(uint64_t, row_rmask, T_ALWAYS, true) /* V2 scan: [row j][lane] slots of the lane's j-th started row */           \
+    X(int32_t, fpl_row_ptr, T_FPL, false) X(int32_t, fpl_col, T_FPL, false) /* frame-per-lane: CSR */                  \
+    X(int32_t, fpl_cslot, T_FPL, false) X(int32_t, fpl_col_ptr, T_FPL, false) /* ... edge's bit_nodes slot, CSC starts */ \
+    X(int32_t, fpl_rows, T_FPL, false)    /* ... rows by length class */                                               \
+    X(int32_t, pair_src, T_PAIRED, true) X(int32_t, pair_col, T_PAIRED, true) /* [k][lane] */                          \
+    X(int32_t, col_orig, T_RELABELLED, true) X(int32_t, col_lab, T_RELABELLED, true) /* label -> bit id and back */    \
+    X(int32_t, ell_lab, T_RELABELLED, true) /* row-ELL in labels (the claim order reads label-ordered frame codes) */
+
 struct DeviceGraph {
     int device = 0;
     int num_cus = 0;
-    DevBuf<uint32_t> slot_meta;
-    DevBuf<int32_t> lane_row0, lane_head, ell_col, row_deg;
-    DevBuf<int32_t> wave_rows;
-    DevBuf<int32_t> lane_nst, lane_epl;
-    DevBuf<uint32_t> slot_meta_ms;                  // V2 min-sum: rows listed by kpos
-    DevBuf<uint64_t> vn_mask, vn_mask_ms;           // V2: [wave][dv_max] slot masks
-    DevBuf<uint64_t> vn_exec, vn_exec_ms;           // V2: [wave][dv_max][slot] lane masks
-    DevBuf<uint32_t> slot_meta2, slot_meta2_ms;     // V2 hybrid: stage index per slot
-    DevBuf<int32_t> hd_bits, hd_dv, stage_off;
-    DevBuf<int32_t> row_orig;   // V2: layout row -> original row (syndrome index)
-    DevBuf<int32_t> part_row0;  // V2 split: first layout row of each part
-    DevBuf<int32_t> xoff;       // V2 split exchange: region starts
-    DevBuf<uint16_t> xbit, xbit_ms;  // ... chunk-local bit per stage position (CSR / kpos layouts)
-    DevBuf<int32_t> iso_bits;
-    DevBuf<uint32_t> vn_rows;  // V2 min-sum bit gather: [n or chunks][2] four u16 layout rows
-    DevBuf<uint32_t> vng_bits, vng_meta2;  // hybrid bit gather: bit order, slot positions
-    DevBuf<uint32_t> vng_rec;  // register-shape bit gather: per slot, the code word's byte offset | shift << 16
-    DevBuf<uint64_t> row_sem;    // V2 scan: [wave][slot][4] START / END / PARK lane masks (+ pad)
-    DevBuf<uint64_t> row_rmask;  // V2 scan: [row j][lane] slots of the lane's j-th started row
-    DevBuf<int32_t> col_orig, col_lab;  // V2 bank relabelling: label -> bit id, bit id -> label
-    DevBuf<int32_t> ell_lab;     // row-ELL in labels (the claim order reads label-ordered frame codes)
-    DevBuf<int32_t> pair_src, pair_col;  // v1 occurrence pairing (unsorted adjacency), [k][lane]
-    DevBuf<int32_t> fpl_row_ptr, fpl_col, fpl_cslot, fpl_col_ptr;  // frame-per-lane: CSR, bit_nodes position per edge, CSC starts
-    DevBuf<int32_t> fpl_rows;  // ... rows by length class
+#define QLDPC_X(type, name, when, digested) DevBuf<type> name;
+    QLDPC_GRAPH_TABLES(QLDPC_X)
+#undef QLDPC_X
     std::mutex mu;     // workspaces (ws), occupancy cache
     std::map<void *, Workspace> ws;
     std::mutex io_mu;  // the host-buffer entry's staging buffers and stream, held copy-in .. copy-out
@@ -238,22 +254,14 @@ struct DeviceGraph {
     }
 };
 
-// The index tables of one graph on the host (layout.hip fills them, capi.hip
-// uploads them to each device; the fields carry DeviceGraph's / DecodeArgs'
-// names).  layout_digest hashes them in this order.
+// The index tables of one graph on the host: one vector per entry of
+// QLDPC_GRAPH_TABLES, under the entry's name (layout.hip fills them, capi.hip
+// uploads them to each device).
 struct GraphTables {
-    std::vector<uint32_t> slot_meta, slot_meta_ms;
-    std::vector<uint64_t> vn_mask, vn_mask_ms, vn_exec, vn_exec_ms;
-    std::vector<uint32_t> slot_meta2, slot_meta2_ms;
-    std::vector<int32_t> hd_bits, hd_dv, stage_off, row_orig, part_row0, xoff;
-    std::vector<uint16_t> xbit, xbit_ms;
-    std::vector<int32_t> lane_row0, wave_rows, lane_head, lane_nst, lane_epl, ell_col, row_deg, iso_bits;
-    std::vector<uint32_t> vn_rows, vng_bits, vng_meta2;
-    std::vector<uint64_t> row_sem;
-    std::vector<uint32_t> vng_rec;
-    std::vector<uint64_t> row_rmask;
-    std::vector<int32_t> pair_src, pair_col, col_orig, col_lab, ell_lab;
-    std::vector<int32_t> fpl_row_ptr, fpl_col, fpl_cslot, fpl_col_ptr, fpl_rows;  // frame-per-lane graphs only (not in the digest)
+#define QLDPC_X(type, name, when, digested) std::vector<type> name;
+    QLDPC_GRAPH_TABLES(QLDPC_X)
+#undef QLDPC_X
+    bool relabelled() const { return !col_orig.empty(); }  // T_RELABELLED
 };
 
 }  // namespace qldpc
