@@ -278,6 +278,14 @@ int qldpc_last_claim_order(qldpc_graph *g, int32_t device, void *stream, int32_t
  * 100) in the SPA message pass's form (atanh2_clip). */
 int qldpc_selftest_math_device(int32_t fn, int32_t count, const double *d_in, double *d_out, void *stream);
 
+/* The same with the clip threshold of fn 8 and fn 9 given (thr > 0, +inf
+ * allowed): fn 8 is tanh(clip(x, thr) / 2.) and fn 9 clip(2. * atanh(x), thr),
+ * evaluated with the constants (min(thr, 44), its tanh, the top of 2 atanh)
+ * that a decode launch with that threshold enabled hands its kernel, computed
+ * by the same host code.  Other fn ignore thr; thr = 100 is the entry above. */
+int qldpc_selftest_math_thr_device(int32_t fn, double thr, int32_t count, const double *d_in, double *d_out,
+                                   void *stream);
+
 /* Thread-local description of the last failure on this thread. */
 const char *qldpc_last_error(void);
 

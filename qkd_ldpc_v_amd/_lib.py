@@ -94,6 +94,7 @@ _SIGNATURES = {
         [_P, _I32, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     ),
     "qldpc_selftest_math_device": (_I32, [_I32, _I32, _P, _P, _P]),
+    "qldpc_selftest_math_thr_device": (_I32, [_I32, ctypes.c_double, _I32, _P, _P, _P]),
     "qldpc_trial_seeds": (_I32, [ctypes.c_uint64, _I32, _P]),
     "qldpc_xoshiro_jump": (_I32, [ctypes.c_uint64, ctypes.c_uint64, _P]),
     "qldpc_xoshiro_state": (_I32, [ctypes.c_uint64, _P]),

@@ -460,6 +460,17 @@ struct PhaseStamps {
 #endif
 };
 
+// The SPA clip constants of a threshold setting, for the decode launch and the
+// math self-test alike (thr_on false: clipping at +inf).
+SpaClip spa_clip(bool thr_on, double thr) {
+    SpaClip c;
+    c.thr = thr_on ? thr : HUGE_VAL;
+    c.lim = c.thr < 44.0 ? c.thr : 44.0;
+    c.t_lim = std::tanh(c.lim / 2.);
+    c.c_top = 2. * std::atanh(0x1.fffffffffffffp-1);
+    return c;
+}
+
 // The kernel arguments of a V1 / V2 launch: what the shape chose decides every
 // table and offset here (frame_order is the claim-order step's).
 DecodeArgs fill_args(const qldpc_graph *g, const DeviceGraph *dg, const Workspace *w, const LaunchShape &s,
@@ -484,9 +495,9 @@ DecodeArgs fill_args(const qldpc_graph *g, const DeviceGraph *dg, const Workspac
         a.ms_clip_later = (fine(p->primary) && (!adapt || fine(p->secondary))) ? 0 : 1;
     }
     {
-        const double lim = (a.thr_on && p->thr < 44.0) ? p->thr : 44.0;
-        a.spa_tlim = std::tanh(lim / 2.);
-        a.spa_ctop = 2. * std::atanh(0x1.fffffffffffffp-1);
+        const SpaClip c = spa_clip(a.thr_on, p->thr);
+        a.spa_tlim = c.t_lim;
+        a.spa_ctop = c.c_top;
     }
     a.batch = f.batch; a.llr = f.llr; a.synd = f.synd; a.bits = f.bits; a.iters = f.iters; a.ok = f.ok; a.post = f.post;
     a.frame_clk = f.frame_clk;
@@ -1052,9 +1063,15 @@ int qldpc_keys_match_device(int32_t batch, int32_t n, const uint8_t *d_alice, co
 }
 
 int qldpc_selftest_math_device(int32_t fn, int32_t count, const double *d_in, double *d_out, void *stream) {
+    return qldpc_selftest_math_thr_device(fn, 100.0, count, d_in, d_out, stream);
+}
+
+int qldpc_selftest_math_thr_device(int32_t fn, double thr, int32_t count, const double *d_in, double *d_out,
+                                   void *stream) {
     if (fn < 0 || fn > 9 || count < 0) return fail(QLDPC_EINVAL, "fn must be 0..9, count >= 0");
+    if (!(thr > 0.)) return fail(QLDPC_EINVAL, "threshold must be > 0");
     if (count > 0 && (!d_in || !d_out)) return fail(QLDPC_EINVAL, "NULL device buffer");
-    hipError_t e = launch_math_selftest(fn, count, d_in, d_out, (hipStream_t)stream);
+    hipError_t e = launch_math_selftest(fn, spa_clip(true, thr), count, d_in, d_out, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "math_selftest");
     return QLDPC_OK;
 }

@@ -393,7 +393,8 @@ __global__ void __launch_bounds__(1024) keys_match_kernel(int n, const uint8_t *
     if (threadIdx.x == 0) match[f] = diff ? 0 : 1;
 }
 
-__global__ void __launch_bounds__(256) math_selftest_kernel(int fn, int count, const double *in, double *out) {
+__global__ void __launch_bounds__(256) math_selftest_kernel(int fn, SpaClip clip, int count, const double *in,
+                                                            double *out) {
     __shared__ ql_exact::Expm1A ctab_a[ql_exact::EXPM1_CLASSES];  // fn 8: the SPA scan's table form
     __shared__ ql_exact::Expm1B ctab_b[ql_exact::EXPM1_CLASSES];
     if (threadIdx.x < ql_exact::EXPM1_CLASSES)
@@ -406,10 +407,8 @@ __global__ void __launch_bounds__(256) math_selftest_kernel(int fn, int count, c
     double y;
     int flag = 0;
     switch (fn) {
-    case 8: y = ql_exact::tanh_half_clip_t(x, 44.0, 1.0, &flag, ctab); break;  // tanh(clip(x, inf) / 2.), tanh(22) = 1
-    case 9:  // the SPA message pass's clip(2. * atanh(x), 100)
-        y = ql_exact::atanh2_clip(x, 100.0, ql_exact::atanh2_full(0x1.fffffffffffffp-1));
-        break;
+    case 8: y = ql_exact::tanh_half_clip_t(x, clip.lim, clip.t_lim, &flag, ctab); break;  // tanh(clip(x, thr) / 2.)
+    case 9: y = ql_exact::atanh2_clip(x, clip.thr, clip.c_top); break;  // the SPA message pass's clip(2. * atanh(x), thr)
     case 0: y = ql_exact::tanh_exact(x); break;
     case 1: y = ql_exact::atanh_exact(x); break;
     case 2: y = ql_exact::expm1_exact(x); break;
@@ -505,9 +504,10 @@ hipError_t launch_build_frames(int n, int m, int max_dc, const int32_t *ell_col,
     return hipGetLastError();
 }
 
-hipError_t launch_math_selftest(int fn, int count, const double *in, double *out, hipStream_t stream) {
+hipError_t launch_math_selftest(int fn, const SpaClip &clip, int count, const double *in, double *out,
+                                hipStream_t stream) {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(math_selftest_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, fn, count, in, out);
+    hipLaunchKernelGGL(math_selftest_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, fn, clip, count, in, out);
     return hipGetLastError();
 }
 

@@ -387,7 +387,18 @@ inline int fpl_cn_grid(const int *class_off) {
 // transposes.  Nothing in it waits on another workgroup.
 hipError_t launch_fpl_chunk(const FplArgs &a, hipStream_t stream);
 
-hipError_t launch_math_selftest(int fn, int count, const double *in, double *out, hipStream_t stream);
+// The host-computed constants of the SPA clipped forms (capi.hip spa_clip()):
+// what a decode launch hands its kernel and what the math self-test evaluates
+// fn 8 / fn 9 with.
+struct SpaClip {
+    double thr;    // the clip threshold, +inf when clipping is off
+    double lim;    // min(thr, 44): tanh(+-b/2) = +-t_lim for |b| >= lim, clipped or not
+    double t_lim;  // glibc tanh(lim / 2.)  (1 for lim = 44)
+    double c_top;  // glibc 2. * atanh(1 - 2^-53)
+};
+
+hipError_t launch_math_selftest(int fn, const SpaClip &clip, int count, const double *in, double *out,
+                                hipStream_t stream);
 hipError_t launch_keys_match(int batch, int n, const uint8_t *alice, const uint8_t *bits,
                              uint8_t *match, hipStream_t stream);
 

@@ -36,6 +36,24 @@ def test_version_and_log_p():
         assert Q.log_p(q) == math.log((1.0 - q) / q)
 
 
+def test_params_threshold_must_be_positive_when_enabled():
+    """check_params, before any device is touched (an empty batch on a
+    host-only graph): an enabled threshold <= 0 or NaN is refused; any thr > 0
+    (+inf too) and any factors, NaN among them, are accepted — the range
+    tests/test_gpu_params.py decodes."""
+    g = Q.Graph(HMatrix.from_check_nodes(4, [[0, 1, 2], [1, 2, 3]]), host_only=True)
+    llr, synd = np.empty((0, 4)), np.empty((0, 2), np.uint8)
+    for thr in (0.0, -0.0, -1.0, -math.inf, math.nan):
+        with pytest.raises(QLDPCError, match="EINVAL.*threshold must be > 0"):
+            g.decode(Q.Params(Q.SPA, 50, True, thr), llr, synd)
+        assert g.decode(Q.Params(Q.SPA, 50, False, thr), llr, synd).bits.shape == (0, 4)  # off: thr is not read
+        assert Q.lib().qldpc_selftest_math_thr_device(8, thr, 0, None, None, None) == -1
+    for thr in (5e-324, 1e-3, 1e300, math.inf):
+        for alg, prim, sec in ((Q.NMSA, math.nan, 0.0), (Q.OMSA, -0.4, 0.0), (Q.ANMSA, 1.2, -3.0)):
+            assert g.decode(Q.Params(alg, 1, True, thr, prim, sec), llr, synd).bits.shape == (0, 4)
+        assert Q.lib().qldpc_selftest_math_thr_device(9, thr, 0, None, None, None) == 0
+
+
 def test_graph_rejects_inconsistent_bit_nodes():
     """bit_nodes must list every edge of check_nodes (any order: the reference's
     occurrence pairing, tests/test_unsorted.py); a column that names a check

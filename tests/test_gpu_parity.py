@@ -69,11 +69,11 @@ def assert_parity(name, alg, prim, sec, qber, batch, max_it=50, thr_on=True, thr
     return out, oi
 
 
-def test_device_exact_math_bitwise(gpu_available):
-    import torch
-
+def math_inputs():
+    """The self-test's input set: the decoder's ranges, both sides of +-1 at
+    every scale, random bit patterns and the special values."""
     rng = np.random.default_rng(11)
-    xs = np.concatenate([
+    return np.concatenate([
         (rng.random(200000) * 2 - 1) * 60.0,
         (rng.random(200000) * 2 - 1) * 2.0,
         1.0 - np.ldexp(rng.random(100000), -rng.integers(0, 60, 100000)),
@@ -81,16 +81,24 @@ def test_device_exact_math_bitwise(gpu_available):
         rng.integers(0, 2**63, 200000, dtype=np.int64).view(np.float64),
         np.array([0.0, -0.0, 1.0, -1.0, 22.0, -22.0, np.inf, -np.inf, np.nan, DBL_MAX, 5e-324]),
     ])
-    refs = {0: math.tanh, 2: math.expm1}
+
+
+def test_device_exact_math_bitwise(gpu_available):
+    import torch
+
+    import ref_python
+
+    xs = math_inputs()
     d_in = torch.from_numpy(xs).cuda()
     d_out = torch.empty_like(d_in)
-    for fn, name in ((0, "tanh"), (1, "atanh"), (2, "expm1"), (3, "log1p"), (6, "tanh_dec"), (7, "atanh_dec"),
-                     (8, "tanh_half_clip_t"), (9, "atanh2_clip")):
+    for fn, name in ((0, "tanh"), (1, "atanh"), (2, "expm1"), (3, "log1p"), (4, "tanh_lin"), (5, "atanh_lin"),
+                     (6, "tanh_dec"), (7, "atanh_dec"), (8, "tanh_half_clip_t"), (9, "atanh2_clip")):
         Q._lib.check(Q.lib().qldpc_selftest_math_device(fn, xs.size, d_in.data_ptr(), d_out.data_ptr(), None),
                      "selftest")
         torch.cuda.synchronize()
         got = d_out.cpu().numpy()
         f = {0: math.tanh, 1: math.atanh, 2: math.expm1, 3: math.log1p, 6: math.tanh, 7: math.atanh,
+             4: ref_python._tanh_lin, 5: ref_python._atanh_lin,  # the reference's piecewise-linear pair (SPA_LIN)
              8: lambda v: math.tanh(v / 2.),  # 8: the SPA scan's table form of tanh(b2c / 2.)
              9: lambda v: v if v != v else max(-100.0, min(100.0, 2. * math.atanh(v)))}[fn]  # 9: clipped 2 atanh
 

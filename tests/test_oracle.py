@@ -74,6 +74,45 @@ def test_oracle_equals_python_restatement(alg, prim, sec, thr_on):
         assert bits_equal_nan(post, np.array(rpost))
 
 
+def _params_grid():
+    from test_gpu_params import POINTS, THRS
+
+    return POINTS, THRS
+
+
+@pytest.mark.parametrize("point", list(_params_grid()[0]))
+def test_oracle_equals_python_restatement_over_thresholds_and_factors(point):
+    """The threshold and factor points of tests/test_gpu_params.py (the GPU is
+    compared with the oracle there) on a 48 x 26 code with a one-bit row (its
+    min2 stays DBL_MAX, SPA sends +-inf before the clip) and an empty row,
+    channel magnitudes log_p and 30: the oracle's reading of the reference's
+    clip order (c2b after the check pass, b2c after the bit pass, the channel
+    LLR never) against the second restatement, bitwise."""
+    from qkd_ldpc_v_amd import HMatrix
+
+    POINTS, THRS = _params_grid()
+    alg, prim, sec = POINTS[point]
+    H0 = _random_code(48, 24, 3, seed=40 + alg)
+    H = HMatrix.from_check_nodes(48, H0.check_nodes + [[7], []])
+    assert (H.n, H.m) == (48, 26)
+    O = Oracle(H)
+    cn, bn = H.check_nodes, H.bit_nodes
+    rng = np.random.default_rng(200 + alg)
+    for trial in range(3):
+        a = rng.integers(0, 2, H.n).astype(np.uint8)
+        b = a.copy()
+        b[rng.choice(H.n, size=2 + trial, replace=False)] ^= 1
+        llr0, s = O.build_frame(a, b, (2 + trial) / H.n)
+        for llr in (llr0, np.where(b != 0, -30.0, 30.0)):
+            for thr in THRS:
+                bits, it, ok, post = O.decode(O.params(alg, 12, True, thr, prim, sec), llr, s)
+                rb, rit, rok, rpost = ref_python.decode(cn, bn, alg, llr.tolist(), s.tolist(), 12, True, thr, prim, sec)
+                what = (point, trial, float(llr[0]), thr)
+                assert (it, ok) == (rit, rok), what
+                assert bits.tolist() == rb, what
+                assert bits_equal_nan(post, np.array(rpost)), what
+
+
 def test_oracle_reproduces_unsorted_slot_pairing():
     """With unsorted bit_nodes lists the reference pairs check->bit slots by
     occurrence order (src/qkd_ldpc_algorithm.cpp:67-69,116-118); the oracle keeps
