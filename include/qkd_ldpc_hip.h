@@ -195,6 +195,51 @@ int qldpc_decode_batch_device(qldpc_graph *g, int32_t device, const qldpc_params
                               uint32_t *d_iters_out, uint8_t *d_synd_ok_out,
                               double *d_posterior_out, void *stream);
 
+/* The same decode with its per-iteration trace: the data the reference prints
+ * under TRACE_DECODING_ALG / TRACE_DECODING_ALG_LLR (src/qkd_ldpc_algorithm.cpp:
+ * 88-99), as arrays.  Frame-per-lane graphs only (QLDPC_LAYOUT_FRAME_PER_LANE):
+ * any other graph returns QLDPC_EUNSUP; build a second graph with that layout.
+ *
+ * Row `it` of frame f exists when the bit pass of iteration `it` ran for f:
+ *   - d_trace_post_out[f][it][0..n) (nullable; batch*max_iterations*n doubles)
+ *     is total_bit_llr after that bit pass, in the reference's bit ids;
+ *   - d_unsat_out[f][it] (nullable; batch*max_iterations words) is the number
+ *     of checks whose parity over the decisions (total <= 0) after that bit
+ *     pass differs from the frame's syndrome bit.  Empty checks count: a
+ *     syndrome bit of 1 on an empty row is one unsatisfied check.
+ * Rows that do not exist read QLDPC_TRACE_NONE and an all-ones NaN (0xFF
+ * bytes): both arrays are filled on the stream before the first launch, and
+ * no kernel writes a row of a frame that has left the decode.
+ *   - SPA / SPA-LIN / NMSA / OMSA: iterations_num rows.
+ *   - ANMSA / AOMSA leave after a check-node pass, before the bit pass:
+ *     iterations_num - 1 rows when syndromes_match (none for a frame whose
+ *     channel decision already matches), max_iterations rows otherwise.
+ * A capped ANMSA / AOMSA frame can show 0 unsatisfied checks in its last row
+ * and still report syndromes_match = 0: the reference never tests the last
+ * decisions of those two (it leaves its loop at the cap).  No other promise
+ * is made about zero counts.
+ * bits / iterations / syndromes_match / posterior are qldpc_decode_batch[_device]'s;
+ * with both trace pointers NULL the call is that decode, launch for launch.
+ * Each traced iteration adds two short launches for the counts and one for the
+ * totals' row.  Arguments are checked in this order: NULL graph, the
+ * parameters, batch < 0, the layout, batch == 0 (OK), NULL buffers; through
+ * batch == 0 no device is touched.
+ * The host entry shards like qldpc_decode_batch and stages the trace arrays on
+ * each shard's device for the call; QLDPC_ENOMEM when they do not fit (then
+ * nothing of the call is in flight). */
+#define QLDPC_TRACE_NONE 0xFFFFFFFFu
+int qldpc_decode_trace_batch_device(qldpc_graph *g, int32_t device, const qldpc_params *p, int32_t batch,
+                                    const double *d_llr, const uint8_t *d_syndrome, uint8_t *d_bits_out,
+                                    uint32_t *d_iters_out, uint8_t *d_synd_ok_out,
+                                    double *d_posterior_out /* nullable */,
+                                    uint32_t *d_unsat_out /* nullable: [batch][max_iterations] */,
+                                    double *d_trace_post_out /* nullable: [batch][max_iterations][n] */,
+                                    void *stream);
+int qldpc_decode_trace_batch(qldpc_graph *g, const qldpc_params *p, int32_t batch, const double *llr,
+                             const uint8_t *syndrome, uint8_t *bits_out, uint32_t *iters_out,
+                             uint8_t *synd_ok_out, double *posterior_out /* nullable */,
+                             uint32_t *unsat_out /* nullable */, double *trace_post_out /* nullable */);
+
 /* ------------------------------------------------ per-trial frame (QKD_LDPC) */
 
 /* QKD_LDPC's frame construction on device (src/qkd_ldpc_algorithm.cpp:

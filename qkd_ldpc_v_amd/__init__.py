@@ -4,9 +4,9 @@ The product is libqkdldpc_hip.so (HIP kernels + C ABI, include/qkd_ldpc_hip.h);
 this package binds it and mirrors the reference's decode interface
 (ColdCloudd/QKD_LDPC_V src/qkd_ldpc_algorithm.hpp).
 """
-from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, Params, QLDPCError, exported_symbols, lib,
-                   log_p, version)
-from .graph import (DecodeOutput, Graph, HMatrix, RatePlan, TrialsOutput, adapt_code_rate, keys_match_device, load_matrix,
+from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, TRACE_NONE, Params, QLDPCError,
+                   exported_symbols, lib, log_p, version)
+from .graph import (DecodeOutput, Graph, HMatrix, RatePlan, TraceOutput, TrialsOutput, adapt_code_rate, keys_match_device, load_matrix,
                     select_punctured_untainted,
                     trial_seeds, trials_device, trials_rate_adapt_device, xoshiro_state)
 from .trials import bsc_frames
@@ -17,5 +17,5 @@ __all__ = [
     "ALGORITHM_NAMES", "ANMSA", "AOMSA", "NMSA", "OMSA", "SPA", "SPA_LIN", "Params", "QLDPCError",
     "exported_symbols", "lib", "log_p", "version", "DecodeOutput", "TrialsOutput", "Graph", "HMatrix", "keys_match_device",
     "trial_seeds", "trials_device", "RatePlan", "adapt_code_rate", "trials_rate_adapt_device", "xoshiro_state",
-    "load_matrix", "bsc_frames",
+    "load_matrix", "bsc_frames", "TraceOutput", "TRACE_NONE",
 ]

@@ -61,6 +61,7 @@ class qldpc_graph_opts(ctypes.Structure):
 
 LAYOUT_AUTO, LAYOUT_FRAME_PER_LANE = 0, 1
 LAYOUTS = {"auto": LAYOUT_AUTO, "frame_per_lane": LAYOUT_FRAME_PER_LANE}
+TRACE_NONE = 0xFFFFFFFF  # QLDPC_TRACE_NONE: a trace row that does not exist
 
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -86,6 +87,9 @@ _SIGNATURES = {
     "qldpc_graph_split_plan": (_I32, [_P, _PI32, _PI32, _PI32]),
     "qldpc_decode_batch": (_I32, [_P, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P]),
     "qldpc_decode_batch_device": (_I32, [_P, _I32, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "qldpc_decode_trace_batch": (_I32, [_P, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qldpc_decode_trace_batch_device": (_I32, [_P, _I32, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, _P]),
     "qldpc_build_frames_device": (_I32, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "qldpc_log_p": (ctypes.c_double, [ctypes.c_double]),
     "qldpc_keys_match_device": (_I32, [_I32, _I32, _P, _P, _P, _P]),

@@ -307,6 +307,9 @@ struct Frames {
     uint8_t *ok;
     double *post;
     uint64_t *frame_clk;
+    // the per-iteration trace (qldpc_decode_trace_batch*, frame-per-lane graphs only; nullable)
+    uint32_t *trace_unsat;  // [batch][max_iterations]
+    double *trace_post;     // [batch][max_iterations][n]
 };
 
 // ---- the steps of a decode call (decode_on, decode_fpl_on) ---------------------
@@ -591,6 +594,13 @@ FplArgs fill_fpl_args(const qldpc_graph *g, const DeviceGraph *dg, const Workspa
     return a;
 }
 
+// The per-iteration trace exists on the frame-per-lane layout alone.
+int trace_layout_check(const qldpc_graph *g) {
+    if (g->variant == VAR_FPL) return QLDPC_OK;
+    return fail(QLDPC_EUNSUP, "the per-iteration trace needs a graph of the frame-per-lane layout "
+                              "(QLDPC_LAYOUT_FRAME_PER_LANE, Graph(H, layout=\"frame_per_lane\"))");
+}
+
 // decode_on for a frame-per-lane graph: deal the frames to tiles of 64, then
 // enqueue every chunk's launch sequence (decoder_fpl.hip).  Nothing is read
 // back: the sequence's length depends on max_iterations and the graph alone.
@@ -608,6 +618,24 @@ int decode_fpl_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, const 
     int rc;
     if ((rc = fpl_workspace(dg, (size_t)chunk, tile_words, stream, &w))) return rc;
     FplArgs a = fill_fpl_args(g, dg, w, p, f, (size_t)chunk);
+    FplTrace trace;
+    trace.unsat = f.trace_unsat;
+    trace.post = f.trace_post;
+    // rows no bit pass writes read QLDPC_TRACE_NONE / an all-ones NaN; the tiles'
+    // counters start at zero (the flush step returns them there)
+    const size_t trace_rows = (size_t)f.batch * (size_t)p->max_iterations;
+    if (trace.unsat) {
+        {
+            std::lock_guard<std::mutex> lk(dg->mu);
+            if ((rc = grow(w->fpl_trace_tiles, (size_t)chunk, stream,
+                           [&] { return w->fpl_trace_cnt.alloc((size_t)chunk * FPL_LANES); })))
+                return rc;
+        }
+        trace.cnt = w->fpl_trace_cnt.get();
+        HIP_TRY(hipMemsetAsync(trace.cnt, 0, (size_t)chunk * FPL_LANES * sizeof(uint32_t), stream));
+        HIP_TRY(hipMemsetAsync(trace.unsat, 0xFF, trace_rows * sizeof(uint32_t), stream));
+    }
+    if (trace.post) HIP_TRY(hipMemsetAsync(trace.post, 0xFF, trace_rows * (size_t)g->n * sizeof(double), stream));
     // the deal: frames in the claim order's sequence, so that a tile's 64 frames
     // look alike (one tile: index order).  Results are per frame either way.
     if ((rc = claim_order(g, dg, w, f, FPL_LANES + 1, stream, &a.frame_order))) return rc;
@@ -617,7 +645,7 @@ int decode_fpl_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, const 
         a.tiles = std::min(chunk, tiles_all - t0);
         a.frame0 = t0 * FPL_LANES;
         a.frames = std::min(f.batch - a.frame0, a.tiles * FPL_LANES);
-        HIP_TRY(launch_fpl_chunk(a, stream));
+        HIP_TRY(launch_fpl_chunk(a, trace, stream));
     }
     return timing_end(g, w, stream);
 }
@@ -630,10 +658,11 @@ int decode_fpl_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, const 
 int decode_on(qldpc_graph *g, DeviceGraph *dg, const qldpc_params *p, int batch, const double *llr,
               const uint8_t *synd, uint8_t *bits, uint32_t *iters, uint8_t *ok, double *post,
               hipStream_t stream, bool codes_ready = false, uint64_t *frame_clk = nullptr,
-              hipEvent_t before_decode = nullptr) {
+              hipEvent_t before_decode = nullptr, uint32_t *trace_unsat = nullptr, double *trace_post = nullptr) {
     if (batch == 0) return QLDPC_OK;
-    const Frames f{batch, llr, synd, bits, iters, ok, post, frame_clk};
+    const Frames f{batch, llr, synd, bits, iters, ok, post, frame_clk, trace_unsat, trace_post};
     if (g->variant == VAR_FPL) return decode_fpl_on(g, dg, p, f, stream, before_decode);
+    if (trace_unsat || trace_post) return trace_layout_check(g);
     const LaunchShape s = launch_shape(*g, p->algorithm, vng_enabled());  // (per call: the knobs are read at launch)
     if (s.rglb && !s.vng)
         return fail(QLDPC_EUNSUP, "this code's min-sum row aggregates need the bit gather (QLDPC_VNG=0 given)");
@@ -963,16 +992,15 @@ int qldpc_decode_batch_device(qldpc_graph *g, int32_t device, const qldpc_params
                      (hipStream_t)stream);
 }
 
-int qldpc_decode_batch(qldpc_graph *g, const qldpc_params *p, int32_t batch, const double *llr,
-                       const uint8_t *syndrome, uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
-                       double *posterior_out) {
-    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
-    if (batch == 0) return QLDPC_OK;
-    if (!llr || !syndrome || !bits_out || !iters_out || !synd_ok_out) return fail(QLDPC_EINVAL, "NULL host buffer");
+// The host-buffer decode behind qldpc_decode_batch and qldpc_decode_trace_batch,
+// which have checked the arguments; the trace arrays (nullable) are staged on
+// each shard's device for the call.
+static int decode_batch_host(qldpc_graph *g, const qldpc_params *p, int32_t batch, const double *llr,
+                             const uint8_t *syndrome, uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
+                             double *posterior_out, uint32_t *unsat_out, double *trace_post_out) {
+    int rc;
     const int G = (int)g->devs.size();
+    if (G == 0) return fail(QLDPC_EINVAL, "a host-only graph cannot decode");
     const int per = (batch + G - 1) / G;
     std::vector<int> rcs(G, QLDPC_OK);
     std::vector<std::string> errs(G);
@@ -997,10 +1025,30 @@ int qldpc_decode_batch(qldpc_graph *g, const qldpc_params *p, int32_t batch, con
                     return r;
                 io.cap_frames = (size_t)nb;
             }
+            // the shard's trace arrays, for this call alone (allocated before anything is enqueued)
+            const size_t rows = (size_t)nb * (size_t)p->max_iterations;
+            DevBuf<uint32_t> d_unsat;
+            DevBuf<double> d_tpost;
+            if ((unsat_out && d_unsat.alloc(rows)) || (trace_post_out && d_tpost.alloc(rows * n))) {
+                (void)hipGetLastError();
+                return fail(QLDPC_ENOMEM, "no device memory for the trace arrays of " + std::to_string(nb) +
+                                              " frames x " + std::to_string(p->max_iterations) + " iterations");
+            }
             HIP_TRY(hipMemcpyAsync(io.llr.get(), llr + f0 * n, nb * n * sizeof(double), hipMemcpyHostToDevice, io.stream));
             HIP_TRY(hipMemcpyAsync(io.synd.get(), syndrome + f0 * m, nb * m, hipMemcpyHostToDevice, io.stream));
             int r = decode_on(g, dg, p, nb, io.llr.get(), io.synd.get(), io.bits.get(), io.iters.get(), io.ok.get(),
-                              posterior_out ? io.post.get() : nullptr, io.stream);
+                              posterior_out ? io.post.get() : nullptr, io.stream, false, nullptr, nullptr,
+                              d_unsat.get(), d_tpost.get());
+            if (!r && unsat_out) {
+                const hipError_t e = hipMemcpyAsync(unsat_out + (size_t)f0 * p->max_iterations, d_unsat.get(),
+                                                    rows * sizeof(uint32_t), hipMemcpyDeviceToHost, io.stream);
+                if (e != hipSuccess) r = hip_fail(e, "trace copy");
+            }
+            if (!r && trace_post_out) {
+                const hipError_t e = hipMemcpyAsync(trace_post_out + (size_t)f0 * p->max_iterations * n, d_tpost.get(),
+                                                    rows * n * sizeof(double), hipMemcpyDeviceToHost, io.stream);
+                if (e != hipSuccess) r = hip_fail(e, "trace copy");
+            }
             if (r) {
                 (void)hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
                 return r;
@@ -1032,6 +1080,53 @@ int qldpc_decode_batch(qldpc_graph *g, const qldpc_params *p, int32_t batch, con
     for (int gi = 0; gi < G; ++gi)
         if (rcs[gi]) return fail(rcs[gi], errs[gi]);
     return QLDPC_OK;
+}
+
+int qldpc_decode_batch(qldpc_graph *g, const qldpc_params *p, int32_t batch, const double *llr,
+                       const uint8_t *syndrome, uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
+                       double *posterior_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!llr || !syndrome || !bits_out || !iters_out || !synd_ok_out) return fail(QLDPC_EINVAL, "NULL host buffer");
+    return decode_batch_host(g, p, batch, llr, syndrome, bits_out, iters_out, synd_ok_out, posterior_out, nullptr,
+                             nullptr);
+}
+
+int qldpc_decode_trace_batch(qldpc_graph *g, const qldpc_params *p, int32_t batch, const double *llr,
+                             const uint8_t *syndrome, uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
+                             double *posterior_out, uint32_t *unsat_out, double *trace_post_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if ((rc = trace_layout_check(g))) return rc;
+    if (batch == 0) return QLDPC_OK;
+    if (!llr || !syndrome || !bits_out || !iters_out || !synd_ok_out) return fail(QLDPC_EINVAL, "NULL host buffer");
+    return decode_batch_host(g, p, batch, llr, syndrome, bits_out, iters_out, synd_ok_out, posterior_out, unsat_out,
+                             trace_post_out);
+}
+
+int qldpc_decode_trace_batch_device(qldpc_graph *g, int32_t device, const qldpc_params *p, int32_t batch,
+                                    const double *d_llr, const uint8_t *d_syndrome, uint8_t *d_bits_out,
+                                    uint32_t *d_iters_out, uint8_t *d_synd_ok_out, double *d_posterior_out,
+                                    uint32_t *d_unsat_out, double *d_trace_post_out, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if ((rc = trace_layout_check(g))) return rc;
+    if (batch == 0) return QLDPC_OK;
+    if (!d_llr || !d_syndrome || !d_bits_out || !d_iters_out || !d_synd_ok_out)
+        return fail(QLDPC_EINVAL, "NULL device buffer");
+    DeviceGraph *dg = find_dev(g, device);
+    if (!dg) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    DeviceScope ds;
+    if ((rc = ds.enter(device))) return rc;
+    return decode_on(g, dg, p, batch, d_llr, d_syndrome, d_bits_out, d_iters_out, d_synd_ok_out, d_posterior_out,
+                     (hipStream_t)stream, false, nullptr, nullptr, d_unsat_out, d_trace_post_out);
 }
 
 int qldpc_build_frames_device(qldpc_graph *g, int32_t device, int32_t batch, const uint8_t *d_alice,

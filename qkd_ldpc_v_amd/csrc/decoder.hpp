@@ -382,10 +382,22 @@ inline int fpl_cn_grid(const int *class_off) {
     for (int c = 0; c < FPL_CLASSES; ++c) g += (class_off[c + 1] - class_off[c] + FPL_CN_WAVES - 1) / FPL_CN_WAVES;
     return g;
 }
+// The per-iteration trace of a frame-per-lane decode (qldpc_decode_trace_batch*):
+// row `it` of a frame is written after the bit pass of iteration `it` while
+// the frame's lane is still in its tile's active mask, and by nothing else.
+constexpr int FPL_TRACE_ROWS = 8;  // rows per wave of the unsatisfied-row count
+struct FplTrace {
+    uint32_t *unsat = nullptr;  // [batch][max_it] rows off their syndrome bit; nullable
+    double *post = nullptr;     // [batch][max_it][n] totals; nullable
+    uint32_t *cnt = nullptr;    // [tiles][64] per-lane counters of the count in flight (zero between launches)
+    bool on() const { return unsat || post; }
+};
 // Enqueue one chunk's whole decode: load transposes, max_it iterations of
 // (check-node pass, settle, bit pass), the closing parity / settle, store
-// transposes.  Nothing in it waits on another workgroup.
-hipError_t launch_fpl_chunk(const FplArgs &a, hipStream_t stream);
+// transposes.  With a trace, each bit pass is followed by the count of
+// unsatisfied rows (two launches) and / or the store of the totals' row.
+// Nothing in it waits on another workgroup.
+hipError_t launch_fpl_chunk(const FplArgs &a, const FplTrace &trace, hipStream_t stream);
 
 // The host-computed constants of the SPA clipped forms (capi.hip spa_clip()):
 // what a decode launch hands its kernel and what the math self-test evaluates

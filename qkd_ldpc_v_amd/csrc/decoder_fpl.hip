@@ -15,6 +15,9 @@
 //                     iteration count
 //   bit pass          one wave per (tile, run of bits): T = L + sum C in
 //                     bit_nodes order, decisions by ballot
+//   trace (on demand) after the bit pass, for the lanes still active: the
+//                     count of rows off their syndrome bit (a count launch
+//                     and a one-wave-per-tile flush) and / or the totals' row
 //
 // No kernel here waits on memory another workgroup writes: ordering comes
 // from stream order alone, so the decode cannot stall on residency, CU masks
@@ -364,7 +367,9 @@ __global__ void __launch_bounds__(256) fpl_store_bits(FplArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(256) fpl_store_post(FplArgs a) {
+// 64 bits x 64 frames of T through LDS, read along frames and written along
+// bits: frame fr's 64 totals go to dst[fr * stride + bit], for the slots in `lanes`.
+__device__ __forceinline__ void fpl_post_rows(const FplArgs &a, double *dst, size_t stride, uint64_t lanes) {
     __shared__ double sh[FPL_LANES][FPL_LANES + 1];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int tile = blockIdx.y, b0 = blockIdx.x * FPL_LANES;
@@ -377,8 +382,57 @@ __global__ void __launch_bounds__(256) fpl_store_post(FplArgs a) {
         const int slot = r * 4 + wave;
         const long long fr = fpl_frame(a, tile, slot);
         const int bit = b0 + lane;
-        if (fr >= 0 && bit < a.n) a.post[(size_t)fr * a.n + bit] = sh[slot][lane];
+        if (fr >= 0 && ((lanes >> slot) & 1) && bit < a.n) dst[(size_t)fr * stride + bit] = sh[slot][lane];
     }
+}
+
+__global__ void __launch_bounds__(256) fpl_store_post(FplArgs a) { fpl_post_rows(a, a.post, (size_t)a.n, ~0ull); }
+
+// ---- trace: what the bit pass of iteration `it` left, for the lanes still active ----
+// The count of rows off their syndrome bit.  A wave walks FPL_TRACE_ROWS rows of
+// the tile (empty rows too: their parity is 0) and each lane sums its own bit of
+// the mismatch masks; the workgroup's waves combine in LDS and one atomic add per
+// lane with a non-zero sum goes to the tile's counters, which fpl_trace_flush
+// reads in the next launch.
+__global__ void __launch_bounds__(256) fpl_trace_count(FplArgs a, FplTrace t) {
+    __shared__ uint32_t sh[4][FPL_LANES];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int tile = blockIdx.y;
+    const uint64_t act = a.active[tile];
+    if (!act) return;  // (the whole workgroup: one tile)
+    const int j0 = (blockIdx.x * 4 + wave) * FPL_TRACE_ROWS;
+    uint32_t sum = 0;
+    for (int j = j0; j < min(j0 + FPL_TRACE_ROWS, a.m); ++j) {
+        const uint64_t mis = row_mismatch(a, tile, j, a.row_ptr[j], a.row_ptr[j + 1], lane) & act;
+        sum += (uint32_t)((mis >> lane) & 1);
+    }
+    sh[wave][lane] = sum;
+    __syncthreads();
+    if (wave == 0) {
+        sum = sh[0][lane] + sh[1][lane] + sh[2][lane] + sh[3][lane];
+        if (sum) atomicAdd(&t.cnt[(size_t)tile * FPL_LANES + lane], sum);
+    }
+}
+
+// One wave per tile: the counters to unsat[frame][it] for the active lanes, and back to zero.
+__global__ void __launch_bounds__(64) fpl_trace_flush(FplArgs a, FplTrace t, int it) {
+    const int tile = blockIdx.x, lane = threadIdx.x;
+    const uint64_t act = a.active[tile];
+    if (!act) return;
+    uint32_t *const c = t.cnt + (size_t)tile * FPL_LANES + lane;
+    if ((act >> lane) & 1) {
+        const long long fr = fpl_frame(a, tile, lane);
+        if (fr >= 0) t.unsat[(size_t)fr * a.max_it + it] = *c;
+    }
+    *c = 0;
+}
+
+// The totals to post[frame][it][bit]: fpl_store_post's transpose, active lanes only.
+__global__ void __launch_bounds__(256) fpl_trace_post(FplArgs a, FplTrace t, int it) {
+    const uint64_t act = a.active[blockIdx.y];
+    if (!act) return;  // (the whole workgroup: one tile)
+    fpl_post_rows(a, t.post + (size_t)it * a.n, (size_t)a.max_it * a.n, act);
 }
 
 template <int ALG, int B>
@@ -406,8 +460,10 @@ void launch_cn(const FplArgs &a, int it, hipStream_t s) {
 
 }  // namespace
 
-hipError_t launch_fpl_chunk(const FplArgs &a, hipStream_t s) {
+hipError_t launch_fpl_chunk(const FplArgs &a, const FplTrace &trace, hipStream_t s) {
     if (a.tiles <= 0 || a.frames <= 0) return hipSuccess;
+    if (trace.unsat && !trace.cnt) return hipErrorInvalidValue;
+    const dim3 g_cnt(((a.m > 0 ? a.m : 1) + 4 * FPL_TRACE_ROWS - 1) / (4 * FPL_TRACE_ROWS), (unsigned)a.tiles);
     const unsigned tiles = (unsigned)a.tiles;
     const bool adaptive = a.alg >= 4;
     const dim3 g_llr((a.n + FPL_LANES - 1) / FPL_LANES, tiles), g_n256((a.n + 255) / 256, tiles);
@@ -429,6 +485,11 @@ hipError_t launch_fpl_chunk(const FplArgs &a, hipStream_t s) {
         // head tested the decisions of iteration it - 1, iterations (it - 1) + 1
         if (adaptive || it > 0) hipLaunchKernelGGL(fpl_settle, dim3(tiles), dim3(64), 0, s, a, adaptive ? it + 1 : it, 1, 0);
         hipLaunchKernelGGL(fpl_bit, g_bit, dim3(256), 0, s, a);
+        if (trace.unsat) {
+            hipLaunchKernelGGL(fpl_trace_count, g_cnt, dim3(256), 0, s, a, trace);
+            hipLaunchKernelGGL(fpl_trace_flush, dim3(tiles), dim3(64), 0, s, a, trace, it);
+        }
+        if (trace.post) hipLaunchKernelGGL(fpl_trace_post, g_llr, dim3(256), 0, s, a, trace, it);
     }
     if (!adaptive) hipLaunchKernelGGL(fpl_parity, g_par, dim3(64 * FPL_CN_WAVES), 0, s, a);
     hipLaunchKernelGGL(fpl_settle, dim3(tiles), dim3(64), 0, s, a, a.max_it, adaptive ? 0 : 1, 1);

@@ -153,6 +153,9 @@ struct Workspace {  // per (device, stream): frame counter + decoder scratch
     // masks of one chunk, capacity in tiles
     DevBuf<uint64_t> fpl;
     size_t fpl_tiles = 0;
+    // ... and of a traced decode: 64 per-lane counters per tile (FplTrace::cnt), capacity in tiles
+    DevBuf<uint32_t> fpl_trace_cnt;
+    size_t fpl_trace_tiles = 0;
     // kernel timing (qldpc_set_kernel_timing): events around the last decode launch
     Event ev0, ev1;
     bool ev_recorded = false;

@@ -92,6 +92,20 @@ class DecodeOutput:
 
 
 @dataclass
+class TraceOutput(DecodeOutput):
+    """A decode and its per-iteration trace (qldpc_decode_trace_batch): row `it`
+    of a frame exists when the bit pass of iteration `it` ran for it; the
+    others read TRACE_NONE / NaN."""
+    unsat: np.ndarray  # uint32[batch, max_it] checks off their syndrome bit after each bit pass
+    trace_posterior: np.ndarray | None  # float64[batch, max_it, n] total_bit_llr after each bit pass
+
+    @property
+    def rows(self) -> np.ndarray:
+        """Trace rows per frame."""
+        return (self.unsat != _lib.TRACE_NONE).sum(axis=1)
+
+
+@dataclass
 class TrialsOutput:
     iterations: np.ndarray  # uint32[count] decoding_result.iterations_num
     synd_ok: np.ndarray     # uint8[count]  decoding_result.syndromes_match
@@ -264,7 +278,7 @@ class Graph:
         return order[:cnt.value].copy(), weight[:cnt.value].copy()
 
     # ---- host-buffer decode (synchronous, shards over the graph's devices) ----
-    def decode(self, params: Params, llr: np.ndarray, syndrome: np.ndarray, posterior: bool = False) -> DecodeOutput:
+    def _host_frames(self, llr, syndrome):
         llr = np.ascontiguousarray(llr, np.float64)
         syn = np.ascontiguousarray(syndrome, np.uint8)
         if llr.ndim == 1:
@@ -274,6 +288,10 @@ class Graph:
         batch = llr.shape[0]
         if llr.shape != (batch, self.n) or syn.shape != (batch, self.m):
             raise ValueError(f"expected llr ({batch},{self.n}) and syndrome ({batch},{self.m})")
+        return llr, syn, batch
+
+    def decode(self, params: Params, llr: np.ndarray, syndrome: np.ndarray, posterior: bool = False) -> DecodeOutput:
+        llr, syn, batch = self._host_frames(llr, syndrome)
         bits = np.empty((batch, self.n), np.uint8)
         iters = np.empty(batch, np.uint32)
         ok = np.empty(batch, np.uint8)
@@ -282,6 +300,25 @@ class Graph:
         check(lib().qldpc_decode_batch(self._g, ctypes.byref(p), batch, ptr(llr), ptr(syn), ptr(bits), ptr(iters),
                                        ptr(ok), ptr(post)), "qldpc_decode_batch")
         return DecodeOutput(bits, iters, ok, post)
+
+    def decode_trace(self, params: Params, llr: np.ndarray, syndrome: np.ndarray, posterior: bool = False,
+                     trace_posterior: bool = False) -> TraceOutput:
+        """decode() with the per-iteration trace (frame-per-lane graphs only):
+        the unsatisfied-check counts, and the posteriors after every bit pass
+        when trace_posterior (batch * max_iterations * n doubles)."""
+        llr, syn, batch = self._host_frames(llr, syndrome)
+        max_it = max(int(params.max_iterations), 0)
+        bits = np.empty((batch, self.n), np.uint8)
+        iters = np.empty(batch, np.uint32)
+        ok = np.empty(batch, np.uint8)
+        post = np.empty((batch, self.n), np.float64) if posterior else None
+        unsat = np.empty((batch, max_it), np.uint32)
+        tpost = np.empty((batch, max_it, self.n), np.float64) if trace_posterior else None
+        p = params.c()
+        check(lib().qldpc_decode_trace_batch(self._g, ctypes.byref(p), batch, ptr(llr), ptr(syn), ptr(bits),
+                                             ptr(iters), ptr(ok), ptr(post), ptr(unsat), ptr(tpost)),
+              "qldpc_decode_trace_batch")
+        return TraceOutput(bits, iters, ok, post, unsat, tpost)
 
     # ---- device-pointer entries (torch tensors as plumbing) ----
     def decode_device(self, params: Params, llr, syndrome, bits, iters, ok, posterior=None, stream=None,
@@ -292,6 +329,17 @@ class Graph:
             self._g, dev, ctypes.byref(p), int(llr.shape[0]), _dp(llr), _dp(syndrome), _dp(bits),
             _dp(iters), _dp(ok), _dp(posterior),
             _stream_ptr(stream, dev)), "qldpc_decode_batch_device")
+
+    def decode_trace_device(self, params: Params, llr, syndrome, bits, iters, ok, posterior=None, unsat=None,
+                            trace_posterior=None, stream=None, device: int | None = None) -> None:
+        """decode_device with the trace: unsat int32 / uint32 [batch, max_it],
+        trace_posterior float64 [batch, max_it, n] (either may be None)."""
+        dev = llr.device.index if device is None else device
+        p = params.c()
+        check(lib().qldpc_decode_trace_batch_device(
+            self._g, dev, ctypes.byref(p), int(llr.shape[0]), _dp(llr), _dp(syndrome), _dp(bits),
+            _dp(iters), _dp(ok), _dp(posterior), _dp(unsat), _dp(trace_posterior),
+            _stream_ptr(stream, dev)), "qldpc_decode_trace_batch_device")
 
     def build_frames_device(self, alice, bob, log_p, llr, syndrome, stream=None, device: int | None = None) -> None:
         dev = alice.device.index if device is None else device

@@ -10,7 +10,11 @@ theta, the passes per frame and the share of exits the gate catches (without
 and with a limit on the gated passes a frame may lose), and the
 smallest theta that catches >= 99 % of the converging frames' exits.
 
-  python tools/exit_gate_stats.py [--workload c2] [--frames 512]
+  python tools/exit_gate_stats.py [--workload c2] [--frames 512] [--source oracle|gpu]
+
+--source gpu takes the counts from the GPU instead: Graph.decode_trace(...).unsat
+on a frame-per-lane graph, one batch for all the frames (the same numbers; the
+oracle decodes one frame at a time).
 """
 import argparse
 import json
@@ -37,6 +41,8 @@ def main():
     ap.add_argument("--max-iterations", type=int, default=50)
     ap.add_argument("--misses", type=int, default=8,
                     help="a limit on the gated passes a frame may lose (measured, not built: DESIGN.md §3.3)")
+    ap.add_argument("--source", default="oracle", choices=["oracle", "gpu"],
+                    help="where the per-iteration counts come from: the CPU oracle's posteriors, or the GPU trace")
     args = ap.parse_args()
     fx, qber, seed = CASES[args.workload]
     H = load_fixture(fx)
@@ -46,15 +52,31 @@ def main():
     ci = np.asarray(H.col_idx, np.int64)
     assert (np.diff(np.asarray(H.row_ptr)) > 0).all()
     before_exit, tracks, iters, oks = [], [], [], []
-    for sd in P.trial_seeds(seed, args.frames):
-        a, b, q = P.trial(H.n, qber, int(sd))
-        lp = np.log((1.0 - q) / q)
-        llr = np.where(b != 0, -lp, lp)
-        s = H.syndrome(a[None, :])[0]
-        _, it, ok, _, tr = O.decode(p, llr, s, trace=True)
-        z = (tr[:it] <= 0.0).astype(np.int64)
-        # c[j] = the count of scan j + 1 (totals after j + 1 iterations)
-        c = ((np.add.reduceat(z[:, ci], rp, axis=1) & 1) != s[None, :]).sum(axis=1)
+
+    def trials():
+        for sd in P.trial_seeds(seed, args.frames):
+            a, b, q = P.trial(H.n, qber, int(sd))
+            lp = np.log((1.0 - q) / q)
+            yield np.where(b != 0, -lp, lp), H.syndrome(a[None, :])[0]
+
+    def oracle_counts():
+        """-> per frame (iterations, ok, c): c[j] = the count of scan j + 1 (totals after j + 1 iterations)"""
+        for llr, s in trials():
+            _, it, ok, _, tr = O.decode(p, llr, s, trace=True)
+            z = (tr[:it] <= 0.0).astype(np.int64)
+            yield it, ok, ((np.add.reduceat(z[:, ci], rp, axis=1) & 1) != s[None, :]).sum(axis=1)
+
+    def gpu_counts():
+        import qkd_ldpc_v_amd as Q
+
+        llr, synd = (np.stack(x) for x in zip(*trials()))
+        out = Q.Graph(H, layout="frame_per_lane").decode_trace(Q.Params(Q.SPA, args.max_iterations, True, 100.0),
+                                                               llr, synd)
+        assert np.array_equal(out.rows, out.iterations)
+        for it, ok, u in zip(out.iterations, out.synd_ok, out.unsat):
+            yield int(it), bool(ok), u[:int(it)].astype(np.int64)
+
+    for it, ok, c in (gpu_counts() if args.source == "gpu" else oracle_counts()):
         assert (c[-1] == 0) == bool(ok)
         iters.append(it)
         oks.append(bool(ok))
