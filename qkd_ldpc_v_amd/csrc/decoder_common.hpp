@@ -216,12 +216,6 @@ struct EdgeMsgsH {
 // wave reads 1 KiB contiguous per group.  The register variant uses a fixed
 // group stride of REG_TSTRIDE lanes and buffer loads whose group offset is a
 // compile-time constant: no per-group address stays live across the kernel.
-#ifdef QL_SLOT_FENCE
-#define QL_SLOT_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define QL_SLOT_BARRIER() ((void)0)
-#endif
-
 template <int R>
 struct MetaSrc {
     __amdgpu_buffer_rsrc_t rs;
@@ -237,13 +231,9 @@ struct MetaSrc {
         for (int g = 0; g < R / 4; ++g) {
             const auto q = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, g * REG_TSTRIDE * 16, 0);
             f(4 * g + 0, (uint32_t)q[0]);
-            QL_SLOT_BARRIER();
             f(4 * g + 1, (uint32_t)q[1]);
-            QL_SLOT_BARRIER();
             f(4 * g + 2, (uint32_t)q[2]);
-            QL_SLOT_BARRIER();
             f(4 * g + 3, (uint32_t)q[3]);
-            QL_SLOT_BARRIER();
         }
     }
 };
@@ -380,38 +370,6 @@ struct MetaSrcW : MetaSrc<R> {
             }
         }
     }
-    // Groups of four slots at least one of which is in the mask: f(g, q, bits)
-    // with q the group's four metadata words and bits its 4-bit slice of the mask.
-    template <typename F>
-    __device__ __forceinline__ void each_group_masked(uint32_t mlo, uint32_t mhi, F &&f) const {
-#pragma unroll
-        for (int g = 0; g < R / 4; ++g) {
-            rotate_prio(g);
-            const uint32_t w = (4 * g < 32) ? mlo : mhi;
-            const uint32_t bits = (w >> ((4 * g) & 31)) & 15u;
-            if (bits) {
-                const auto q = __builtin_amdgcn_raw_buffer_load_b128(this->rs, this->voff, g * REG_TSTRIDE * 16, 0);
-                f(g, q, bits);
-            }
-        }
-    }
-    // Same, with the next group's metadata requested before this group's work
-    // (a VN phase does little per group: one memory latency per group would
-    // otherwise be exposed on every wave at once).
-    template <typename F>
-    __device__ __forceinline__ void each_group_masked_pf(uint32_t mlo, uint32_t mhi, F &&f) const {
-        auto q = __builtin_amdgcn_raw_buffer_load_b128(this->rs, this->voff, 0, 0);
-#pragma unroll
-        for (int g = 0; g < R / 4; ++g) {
-            const uint32_t w = (4 * g < 32) ? mlo : mhi;
-            const uint32_t bits = (w >> ((4 * g) & 31)) & 15u;
-            const auto qn = (g + 1 < R / 4)
-                                ? __builtin_amdgcn_raw_buffer_load_b128(this->rs, this->voff, (g + 1) * REG_TSTRIDE * 16, 0)
-                                : q;
-            if (bits) f(g, q, bits);
-            q = qn;
-        }
-    }
     // Batches of NB consecutive groups at least one of which is in the mask:
     // f(g, q[NB], nv) — q[j] the metadata of group g + j, nv the groups that
     // exist.  The next batch's first group's metadata is requested before
@@ -441,21 +399,6 @@ struct MetaSrcW : MetaSrc<R> {
                                 : q0;
             if (bits) f(g, q, (NG - g < NB) ? NG - g : NB);
             q0 = qn;
-        }
-    }
-    template <typename F>
-    __device__ __forceinline__ void each_masked(uint32_t mlo, uint32_t mhi, F &&f) const {
-#pragma unroll
-        for (int g = 0; g < R / 4; ++g) {
-            const uint32_t w = (4 * g < 32) ? mlo : mhi;
-            const int b = (4 * g) & 31;
-            if ((w >> b) & 15u) {
-                const auto q = __builtin_amdgcn_raw_buffer_load_b128(this->rs, this->voff, g * REG_TSTRIDE * 16, 0);
-                if ((w >> b) & 1u) f(4 * g + 0, (uint32_t)q[0]);
-                if ((w >> (b + 1)) & 1u) f(4 * g + 1, (uint32_t)q[1]);
-                if ((w >> (b + 2)) & 1u) f(4 * g + 2, (uint32_t)q[2]);
-                if ((w >> (b + 3)) & 1u) f(4 * g + 3, (uint32_t)q[3]);
-            }
         }
     }
 };

@@ -31,32 +31,8 @@ constexpr int V2_CTRL = 16;  // s_frame, mismatch epoch
 #define QL_VN_BATCH 2
 #endif
 constexpr int V2_VN_BATCH = QL_VN_BATCH;  // VN phases: slot groups per LDS round trip
-#ifndef QL_SPLIT_DEFER
-// split frames: the exit test after the message pass, a workgroup barrier
-// between scan and message pass (1); 0: the test first (A/B builds only; the
-// round-5 wave-local-fence arm measured equal and was removed)
-#define QL_SPLIT_DEFER 1
-#endif
-static_assert(QL_SPLIT_DEFER == 0 || QL_SPLIT_DEFER == 1, "QL_SPLIT_DEFER: 0 or 1");
-#ifndef QL_MSG_PF
-#define QL_MSG_PF 1  // stage-writing message passes request the next group's metadata early
-#endif
 #ifndef QL_XG_UNROLL
 #define QL_XG_UNROLL 4  // split exchange gather: terms per thread per load round (8: spills, 10% slower C4)
-#endif
-#ifndef QL_GH_PF
-#define QL_GH_PF 1  // hybrid bit gather: the next bit's entry requested one bit ahead
-#endif
-#ifndef QL_SPLIT_TANH_W
-#define QL_SPLIT_TANH_W 1  // split-frame SPA: tanh's expm1 table in the word form (exact_math.h Expm1Bw)
-#endif
-#ifndef QL_HOIST_LLR
-#define QL_HOIST_LLR 0  // (A/B) SPA message pass: the kpos-0 channel LLR requested first
-#endif
-#ifdef QL_NO_ROWSCAN
-constexpr bool V2_ROWSCAN_ON = false;  // A/B only: SPA scan with per-slot flag bookkeeping
-#else
-constexpr bool V2_ROWSCAN_ON = true;
 #endif
 
 __host__ __device__ inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -159,7 +135,7 @@ __device__ __forceinline__ V2Layout v2_layout(const DecodeArgs &a, bool minsum) 
 // register shape V2_R_TIGHT, and the frame's LDS image plus the slots fit.
 __host__ __device__ inline bool v2_use_rl(int alg, int R, int RG, bool split, int n, int m, int T) {
     if (alg > 1 || R != V2_R_TIGHT || RG != 0 || split || T > REG_TSTRIDE) return false;
-    return V2Layout(n, m, (n + 3) / 4, T, false, false, V2_RL, V2_ROWSCAN_ON).bytes <= 160 * 1024;
+    return V2Layout(n, m, (n + 3) / 4, T, false, false, V2_RL, true).bytes <= 160 * 1024;
 }
 // Split frames keep their totals in global memory, so a part's LDS holds only
 // its rows: the SPA family keeps v2_rl_split(pl) of the 40 message slots there
@@ -255,7 +231,7 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
     // SPA row products are unsigned until their END, where the syndrome sign
     // goes on (sign flips commute with round-to-nearest); min-sum rows get
     // their sign at END and (ANMSA/AOMSA) their mismatch flag after the loop.
-    constexpr bool ROWSCAN = V2_ROWSCAN_ON && !SPLIT && RG == 0;
+    constexpr bool ROWSCAN = !SPLIT && RG == 0;
 
     const int tid = threadIdx.x;
     const int T = a.T, n = a.n, m = a.m, nc = a.nc;
@@ -370,7 +346,8 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
         }
     }
     // SPA: the expm1 class table of tanh_half_clip_t, once per workgroup (the
-    // frame loop's first barrier orders it before any scan)
+    // frame loop's first barrier orders it before any scan); split frames
+    // take it in the word form (exact_math.h Expm1Bw)
     // (two arrays of 16-byte entries: A at L.ctab, B right after A)
     // (entries of 32 bytes: A = {X3, X4} then B = {B, C, k << 20}; see exact_math.h)
     ql_exact::Expm1A *const ctab_a = reinterpret_cast<ql_exact::Expm1A *>(smem + L.ctab);
@@ -378,7 +355,7 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
     const ql_exact::Expm1Tab ctab{ctab_a, ctab_b, 2};
     if constexpr (ALG == 0) {
         if (tid < ql_exact::EXPM1_CLASSES)
-            ql_exact::expm1_class<SPLIT && QL_SPLIT_TANH_W>(tid + ql_exact::EXPM1_K_MIN, &ctab_a[2 * tid], &ctab_b[2 * tid]);
+            ql_exact::expm1_class<SPLIT>(tid + ql_exact::EXPM1_K_MIN, &ctab_a[2 * tid], &ctab_b[2 * tid]);
     }
 #ifdef QL_PHASE_STAMPS
     uint64_t st_acc[NUM_STAMPS];
@@ -466,15 +443,6 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
             group_sync(gsync, gsync_n, a.split_err);                         \
         } else {                                                             \
             __syncthreads();                                                 \
-        }                                                                    \
-    } while (0)
-        // split frames between a wave's scan and its own message pass
-#define split_local_sync()                                                   \
-    do {                                                                     \
-        if constexpr (SPLIT && QL_SPLIT_DEFER) {                             \
-            __syncthreads();                                                 \
-        } else {                                                             \
-            psync();                                                         \
         }                                                                    \
     } while (0)
         const int bit_lo = SPLIT ? (int)((long long)n * rank / a.split_k) : 0;
@@ -734,12 +702,12 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                     uint2 e_n = make_uint2(0u, 0u);
                     if (tid < n) e_n = ld2(vb_rs, (uint32_t)tid * 8u);
                     for (int i = tid; i < n; i += T) {
-                        const uint2 e = QL_GH_PF ? e_n : ld2(vb_rs, (uint32_t)i * 8u);
+                        const uint2 e = e_n;
                         const int b = (int)e.x;
                         const uint32_t c0 = e.y & 0xFFFFFFu;
                         const int dvb = (int)(e.y >> 24);
                         uint2 rr = ld2(vr_rs, c0 * 8u);
-                        if (QL_GH_PF && i + T < n) e_n = ld2(vb_rs, (uint32_t)(i + T) * 8u);
+                        if (i + T < n) e_n = ld2(vb_rs, (uint32_t)(i + T) * 8u);
                         double sacc = llr_of(b);
                         for (int kc = 0; kc < dvb; kc += 4) {
                             const uint32_t ch = c0 + (uint32_t)(kc >> 2);
@@ -1027,7 +995,9 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                 if (head > 0) rowI[row0] = make_int2(pcnt + head, ppar ^ hpar ^ s_row0);
             }
             STAMP(ST_CN1);
-            split_local_sync();  // (no exit test in iteration 0)
+            // (no exit test in iteration 0; split frames: a wave's message pass
+            // reads only rows its own wave scanned)
+            __syncthreads();
             STAMP(ST_CN1_WAIT);
             r = row0;
             auto message0 = [&](int k, uint32_t mt, uint32_t mt2) {
@@ -1116,7 +1086,7 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                     if constexpr (SPA_FAM) {
                         double t = b;
                         if constexpr (ALG == 0) {
-                            if (compute) t = ql_exact::tanh_half_clip_t<SPLIT && QL_SPLIT_TANH_W>(b, lim_it, tlim_it, &div_unsafe, ctab);  // (:60)
+                            if (compute) t = ql_exact::tanh_half_clip_t<SPLIT>(b, lim_it, tlim_it, &div_unsafe, ctab);  // (:60)
                         } else {
                             if (compute) t = tanh_lin(b / 2.);
                         }
@@ -1214,7 +1184,7 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                     // into tanh_half_clip with the iteration's (lim, thr).
                     const double b = tv - c2b.get_seq(k);
                     double t = b;
-                    if (compute) t = ql_exact::tanh_half_clip_t<SPLIT && QL_SPLIT_TANH_W>(b, lim_it, tlim_it, &div_unsafe, ctab);  // tanh(b2c / 2.) (:60)
+                    if (compute) t = ql_exact::tanh_half_clip_t<SPLIT>(b, lim_it, tlim_it, &div_unsafe, ctab);  // tanh(b2c / 2.) (:60)
                     c2b.set(k, t);
                     const double st = (s ? -1. : 1.) * t;  // (:57-62)
                     acc = start ? st : acc * t;
@@ -1258,11 +1228,7 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                 }
             };
             if constexpr (SPLIT) {  // totals in global memory: a group's four loads issued together
-#ifdef QL_DIAG_SCAN_HOT  // (diagnostic A/B only: every total read from 256 L1-hot entries — wrong decodes)
-                meta.each_upto_tv(epl, [&](uint32_t mt) { return total[(int)(mt & 255)]; }, scan_slot);
-#else
                 meta.each_upto_tv(epl, [&](uint32_t mt) { return total[(int)(mt & META_COL_MASK)]; }, scan_slot);
-#endif
             } else {
                 meta.each_upto(epl, [&](int k, uint32_t mt) { scan_slot(k, mt, tot_at(mt)); });
             }
@@ -1318,9 +1284,9 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
             // only the stage: the totals the outputs read are untouched), to
             // the barrier before the gather: one group barrier per iteration
             // fewer, one wasted message pass on the last.  The message pass
-            // reads only rows its own wave scanned.
-            const bool defer = SPLIT && QL_SPLIT_DEFER && compute;
-            if (defer) split_local_sync();
+            // reads only rows its own wave scanned: a workgroup barrier.
+            const bool defer = SPLIT && compute;
+            if (defer) __syncthreads();
             else psync();
             STAMP(ST_CN1_WAIT);
             const bool anymis =
@@ -1378,16 +1344,6 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                     if (k > 0) r += (mt & META_START) ? 1 : 0;
                 }
                 double c;
-                // SPA on one-workgroup register shapes: a kpos-0 edge's channel
-                // LLR (two dependent LDS reads) is requested before the message
-                // math, so its latency hides behind it (VN phase 0 below)
-                constexpr bool HOIST = QL_HOIST_LLR && ALG == 0 && !SPLIT && !VNG && !GATHER;
-                bool kpos0 = false;
-                double lv0 = 0.0;
-                if constexpr (HOIST) {
-                    kpos0 = __builtin_amdgcn_inverse_ballot_w64(vn_exec[k]);
-                    if (kpos0) lv0 = llr_of((int)(mt & META_COL_MASK));
-                }
                 if constexpr (ALG == 0) {
                     // 2. * atanh(rp / t) (:66-68) and the clip (:73-74) in one
                     const double ra = rowA[r], tk = c2b.get_seq(k);
@@ -1428,16 +1384,12 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
                     }
                 }
                 if constexpr (SPA_FAM && ALG != 0) c = clip_msg(c, thr);  // (:73-74)
-                if constexpr (HOIST) {
-                    c2b.set(k, c);
-                    if (kpos0) tot_at(mt) = lv0 + c;  // first term of std::accumulate (:78)
-                } else {
-                    emit(k, mt, mt2, c);
-                }
+                emit(k, mt, mt2, c);
             };
-            if constexpr (GATHER && QL_MSG_PF) {  // (global stage stores per slot)
+            // (global stage stores per slot: the next group's metadata is requested early)
+            if constexpr (GATHER) {
                 meta.each_upto2_pf(epl, meta2_rs, message);
-            } else if constexpr (GATHER || VNG) {
+            } else if constexpr (VNG) {
                 meta.each_upto2(epl, meta2_rs, message);
             } else {
                 meta.each_upto(epl, [&](int k, uint32_t mt) { message(k, mt, 0u); });
@@ -1480,7 +1432,6 @@ __global__ void __launch_bounds__(v2_max_threads<R>()) decode_v2_kernel(DecodeAr
 #endif
 }
 #undef psync
-#undef split_local_sync
 
 // Palette + 2-bit codes of each frame's LLRs (one workgroup per frame).  Wave 0
 // collects up to 4 distinct values (bitwise) in first-occurrence order; a frame
@@ -1618,8 +1569,7 @@ LaunchShape v2_launch_shape(const V2ShapeQuery &q) {
         s.lds_bytes = V2Layout(q.n, q.rows, (q.n + 3) / 4, q.threads, minsum, true, s.RL, false, q.gcb, q.threads).bytes;
     } else {
         s.RL = v2_use_rl(q.alg, q.R, q.RG, false, q.n, q.rows, q.threads) ? V2_RL : 0;
-        s.lds_bytes = V2Layout(q.n, s.rows_lds, (q.n + 3) / 4, q.threads, minsum, false, s.RL,
-                               V2_ROWSCAN_ON && q.RG == 0).bytes;
+        s.lds_bytes = V2Layout(q.n, s.rows_lds, (q.n + 3) / 4, q.threads, minsum, false, s.RL, q.RG == 0).bytes;
     }
     return s;
 }

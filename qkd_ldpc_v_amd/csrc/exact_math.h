@@ -583,13 +583,8 @@ QL_HD double atanh_dec(double x) {
 //   * b / 2 is never formed on the common path: |b| = 2|x| is the expm1
 //     argument magnitude itself; 2 * copysign(0.5 * y, p) == copysign(y, p).
 // A divergent `if` on a rare lane condition: the wave skips the body (exec
-// empty) unless one of its lanes needs it.  QL_COUNT_COMMON drops the rare
-// bodies — for instruction counting only, never in a product build.
-#if defined(QL_COUNT_COMMON)
-#define QL_RARE(c) if (false)
-#else
+// empty) unless one of its lanes needs it.
 #define QL_RARE(c) if (__builtin_expect((c), 0))
-#endif
 
 // tanh(b / 2.) bit-identical to glibc.  Common path: 2^-54 <= |b| < 44 (that
 // is 2^-55 <= |x| < 22 for x = b/2, computed exactly as |b|/2).
