@@ -379,7 +379,8 @@ int qldpc_trials_device(int32_t n, double qber, int32_t batch, const uint64_t *d
  * (the reference's WARNING + skip) return QLDPC_OK with zero counts.
  * punctured_out / shortened_out need capacity n (NULL: counts only).
  * qldpc_rate_plan_create: the position classes of one (punctured, shortened)
- * pair, replicated on the graph's devices.
+ * pair, replicated on the graph's devices (a host-only graph: on none, and no
+ * device is touched).
  * qldpc_trials_rate_adapt_device: qldpc_trials_device plus, per trial, the
  * 2 * n_punct further draws QKD_LDPC_RATE_ADAPT takes for punctured positions
  * (src/qkd_ldpc_algorithm.cpp:1148-1157) -> d_punct_alice/bob [batch*n_punct].
@@ -422,6 +423,73 @@ int qldpc_qkd_ldpc_rate_adapt_batch_device(qldpc_graph *g, const qldpc_rate_plan
                                            double *d_llr_ws, uint8_t *d_synd_ws, uint8_t *d_bits_out,
                                            uint32_t *d_iters_out, uint8_t *d_synd_ok_out, uint8_t *d_keys_match_out,
                                            void *stream);
+
+/* ---- Two parties: Alice's syndromes, Bob's decode from his own key -------------
+ * The entries above restate the reference's simulation, which holds both keys
+ * side by side.  In error reconciliation itself neither side sees the other's
+ * key: Alice publishes a syndrome, Bob decodes from his key, the received
+ * syndrome and a QBER estimate.  These entries are that per-party cut of the
+ * frame construction; what they write is byte for byte what the fused entries
+ * write for the same inputs.
+ *
+ * Key bytes must be 0 or 1: only bit 0 of each byte is read, as in the fused
+ * builders.
+ *
+ * Key layout with a plan: d_key is [batch][n] and only the first
+ * n_key = n - n_punct - n_short entries of a row are used, exactly as
+ * QKD_LDPC_RATE_ADAPT reads alice_bit_array[n]
+ * (src/qkd_ldpc_algorithm.cpp:1169-1172), so the buffers
+ * qldpc_trials_rate_adapt_device fills pass unchanged.  Without a plan the
+ * key is the frame.
+ *
+ * qldpc_syndrome_batch_device (Alice): d_syndrome_out[f] = H * x_f, where x_f
+ * is her key or, with a plan, her extended key: key bits at the plan's key
+ * positions in order, d_punct_fill[f][k] at the k-th punctured position (her
+ * private randomness, :1148-1157; [batch*n_punct], NULL allowed when there is
+ * no plan or n_punct == 0) and 0 at shortened positions.  d_key_ext_out
+ * (nullable, [batch*n]) receives x_f when a plan is given (without one it is
+ * not written: the key is the frame).
+ *
+ * qldpc_reconcile_batch_device (Bob): qldpc_qkd_ldpc[_rate_adapt]_batch_device
+ * minus Alice — Bob's LLRs from d_key and d_log_p (+-log_p[f]; with a plan
+ * 1e-4 at punctured positions whatever he would draw there, :1153-1155, and
+ * DBL_MAX at shortened ones), then the decode against d_syndrome ([batch*m],
+ * read only).  d_llr_ws nullable as in qldpc_qkd_ldpc_batch_device;
+ * d_posterior_out nullable as in qldpc_decode_batch_device.  Works on every
+ * graph layout.  d_log_p as in qldpc_build_frames_device (qldpc_log_p).
+ *
+ * qldpc_extract_key_device: the inverse of the extension — d_key_out[f]
+ * ([batch*n_key]) = d_bits[f] ([batch*n], a decoded frame or an extended key)
+ * at the plan's key positions, in order.  Needs a plan.
+ *
+ * qldpc_syndrome_batch / qldpc_reconcile_batch: the same on HOST buffers,
+ * synchronous, sharded over the graph's devices like qldpc_decode_batch (the
+ * plan must live on every device of the graph).  Only key bytes, log_p and
+ * syndromes cross to the device: n + m + 8 bytes per frame instead of the
+ * 8 n + m of host-built LLRs.
+ *
+ * Arguments are checked in this order wherever the step applies: NULL graph,
+ * the parameters, batch < 0, batch == 0 (OK), NULL buffers (and the plan of
+ * the extract entry), the plan on the device, the device, the LDS fit
+ * (QLDPC_EUNSUP beyond n of about 1.3 million; Alice with a plan about 650k).
+ * Through batch == 0 no device is touched. */
+int qldpc_syndrome_batch_device(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t device,
+                                int32_t batch, const uint8_t *d_key, const uint8_t *d_punct_fill /* nullable */,
+                                uint8_t *d_key_ext_out /* nullable */, uint8_t *d_syndrome_out, void *stream);
+int qldpc_reconcile_batch_device(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t device,
+                                 const qldpc_params *p, int32_t batch, const uint8_t *d_key, const double *d_log_p,
+                                 const uint8_t *d_syndrome, double *d_llr_ws /* nullable */, uint8_t *d_bits_out,
+                                 uint32_t *d_iters_out, uint8_t *d_synd_ok_out,
+                                 double *d_posterior_out /* nullable */, void *stream);
+int qldpc_extract_key_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t batch,
+                             const uint8_t *d_bits, uint8_t *d_key_out, void *stream);
+int qldpc_syndrome_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t batch,
+                         const uint8_t *key, const uint8_t *punct_fill /* nullable */,
+                         uint8_t *key_ext_out /* nullable */, uint8_t *syndrome_out);
+int qldpc_reconcile_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, const qldpc_params *p,
+                          int32_t batch, const uint8_t *key, const double *log_p, const uint8_t *syndrome,
+                          uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
+                          double *posterior_out /* nullable */);
 
 /* ---- Simulation-driver helpers ----------------------
  * qldpc_sort_permutation: the order std::sort (libstdc++, not stable) leaves a

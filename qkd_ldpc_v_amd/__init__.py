@@ -3,6 +3,11 @@
 The product is libqkdldpc_hip.so (HIP kernels + C ABI, include/qkd_ldpc_hip.h);
 this package binds it and mirrors the reference's decode interface
 (ColdCloudd/QKD_LDPC_V src/qkd_ldpc_algorithm.hpp).
+
+Two parties: Alice publishes Graph.syndrome(keys[, plan, punct_fill]); Bob
+decodes with Graph.reconcile(params, keys, log_p, syndrome[, plan]) from his own
+key and the received syndrome (device forms: syndrome_device, reconcile_device,
+extract_key_device).  Neither call sees the other side's key.
 """
 from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, TRACE_NONE, Params, QLDPCError,
                    exported_symbols, lib, log_p, version)

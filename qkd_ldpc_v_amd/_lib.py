@@ -114,6 +114,12 @@ _SIGNATURES = {
     "qldpc_build_frames_rate_adapt_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qldpc_qkd_ldpc_rate_adapt_batch_device": (_I32, [_P, _P, _I32, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P,
                                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qldpc_syndrome_batch_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "qldpc_reconcile_batch_device": (_I32, [_P, _P, _I32, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P,
+                                            _P, _P, _P]),
+    "qldpc_extract_key_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _P]),
+    "qldpc_syndrome_batch": (_I32, [_P, _P, _I32, _P, _P, _P, _P]),
+    "qldpc_reconcile_batch": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P, _P]),
     "qldpc_trials_device": (_I32, [_I32, ctypes.c_double, _I32, _P, ctypes.c_uint64, _P, _P,
                                    ctypes.POINTER(ctypes.c_double), _P]),
     "qldpc_run_trials": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), ctypes.c_double, _I32, _P, ctypes.c_uint64,

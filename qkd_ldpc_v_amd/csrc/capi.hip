@@ -697,6 +697,94 @@ const qldpc_rate_plan::Dev *plan_dev(const qldpc_rate_plan *plan, int device) {
     return pd;
 }
 
+// The host-buffer entries' sharding: contiguous slices of the batch over the
+// graph's devices, one host thread per shard, no collectives; the first error
+// of any shard is reported.  body(dg, io, f0, nb) runs with the shard's device
+// current, its staging stream created and io_mu held: one call at a time per
+// device owns the staging buffers and their stream, from the copy-in to the
+// completed copy-out, so concurrent host threads on one shared graph (the
+// reference's thread pool over trials) serialise there instead of overwriting
+// each other's frames.
+template <typename Body>
+int for_each_shard(qldpc_graph *g, int32_t batch, const char *host_only_msg, Body body) {
+    int rc;
+    const int G = (int)g->devs.size();
+    if (G == 0) return fail(QLDPC_EINVAL, host_only_msg);
+    const int per = (batch + G - 1) / G;
+    std::vector<int> rcs(G, QLDPC_OK);
+    std::vector<std::string> errs(G);
+    auto work = [&](int gi) {
+        DeviceGraph *dg = g->devs[gi].get();
+        const int f0 = gi * per, f1 = std::min(batch, f0 + per), nb = f1 - f0;
+        if (nb <= 0) return;
+        auto shard = [&]() -> int {
+            HIP_TRY(hipSetDevice(dg->device));
+            std::lock_guard<std::mutex> io_lk(dg->io_mu);
+            HostIO &io = dg->io;
+            if (!io.stream) HIP_TRY(hipStreamCreateWithFlags(io.stream.put(), hipStreamNonBlocking));
+            return body(dg, io, f0, nb);
+        };
+        const int r = shard();
+        rcs[gi] = r;
+        if (r) errs[gi] = g_last_error;
+    };
+    {
+        DeviceScope restore;
+        if ((rc = restore.save())) return rc;
+        if (G == 1) {
+            work(0);
+        } else {
+            std::vector<std::thread> th;
+            for (int gi = 0; gi < G; ++gi) th.emplace_back(work, gi);
+            for (auto &t : th) t.join();
+        }
+    }
+    for (int gi = 0; gi < G; ++gi)
+        if (rcs[gi]) return fail(rcs[gi], errs[gi]);
+    return QLDPC_OK;
+}
+
+// The per-party kernels keep a party's key (Alice with a plan: her fill and the
+// extended key too) in LDS as bit words (decoder.hpp alice_syndrome_lds /
+// bob_frames_lds): refuse larger graphs with a message instead of a launch error.
+int party_fits(const qldpc_graph *g, bool alice, int n_punct /* < 0: no plan */) {
+    const size_t lds = alice ? alice_syndrome_lds(g->n, n_punct) : bob_frames_lds(g->n);
+    if (lds <= LDS_MAX_BYTES) return QLDPC_OK;
+    return fail(QLDPC_EUNSUP, "n = " + std::to_string(g->n) + ": the per-party frame kernels keep the key in LDS (" +
+                                  std::to_string(lds) + " bytes > " + std::to_string(LDS_MAX_BYTES) +
+                                  "); decode such frames through qldpc_decode_batch[_device] with host-built LLRs");
+}
+
+// qkd_ldpc_window minus Alice, for `batch` device-resident frames on `s` (the
+// current device is dg's): Bob's frames from his key alone, then the decode
+// against the syndrome he received.  V2 decoders read the palette codes the
+// frame kernel writes into the stream's workspace; the others read llr[] from
+// d_llr_ws or, when it is NULL, from the stream workspace's.
+int reconcile_window(qldpc_graph *g, DeviceGraph *dg, const qldpc_rate_plan::Dev *pd, const qldpc_params *p, int batch,
+                     const uint8_t *d_key, const double *d_log_p, const uint8_t *d_synd, double *d_llr_ws,
+                     uint8_t *d_bits_out, uint32_t *d_iters_out, uint8_t *d_synd_ok_out, double *d_post_out,
+                     hipStream_t s) {
+    const bool v2 = g->variant == VAR_V2;
+    uint8_t *codes = nullptr, *pal_ok = nullptr;
+    double *palette = nullptr;
+    double *llr = d_llr_ws;
+    {
+        std::lock_guard<std::mutex> lk(dg->mu);
+        Workspace *w = workspace(dg, s);
+        if (v2) {
+            if (int r = ensure_codes(g, w, batch, s)) return r;
+            codes = w->codes.get(); palette = w->palette.get(); pal_ok = w->pal_ok.get();
+        } else if (!llr) {
+            if (int r = grow(w->llr_ws_frames, (size_t)batch, s, [&] { return w->llr_ws.alloc((size_t)batch * g->n); }))
+                return r;
+            llr = w->llr_ws.get();
+        }
+    }
+    HIP_TRY(launch_bob_frames(g->n, pd ? pd->cls.get() : nullptr, pd ? pd->src.get() : nullptr, batch, d_key, d_log_p,
+                              llr, codes, palette, pal_ok, dg->col_orig.get(), s));
+    return decode_on(g, dg, p, batch, llr, d_synd, d_bits_out, d_iters_out, d_synd_ok_out, d_post_out, s, v2);
+}
+
 }  // namespace
 
 // QKD_LDPC's (plan == NULL) or QKD_LDPC_RATE_ADAPT's per-trial window for
@@ -998,33 +1086,10 @@ int qldpc_decode_batch_device(qldpc_graph *g, int32_t device, const qldpc_params
 static int decode_batch_host(qldpc_graph *g, const qldpc_params *p, int32_t batch, const double *llr,
                              const uint8_t *syndrome, uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
                              double *posterior_out, uint32_t *unsat_out, double *trace_post_out) {
-    int rc;
-    const int G = (int)g->devs.size();
-    if (G == 0) return fail(QLDPC_EINVAL, "a host-only graph cannot decode");
-    const int per = (batch + G - 1) / G;
-    std::vector<int> rcs(G, QLDPC_OK);
-    std::vector<std::string> errs(G);
-    auto work = [&](int gi) {
-        DeviceGraph *dg = g->devs[gi].get();
-        const int f0 = gi * per, f1 = std::min(batch, f0 + per), nb = f1 - f0;
-        if (nb <= 0) return;
-        const size_t n = (size_t)g->n, m = (size_t)g->m;
-        // One call at a time per device owns the staging buffers and their
-        // stream, from the copy-in to the completed copy-out: concurrent host
-        // threads on one shared graph (the reference's thread pool over
-        // trials) serialise here instead of overwriting each other's frames.
-        auto body = [&]() -> int {
-            HIP_TRY(hipSetDevice(dg->device));
-            std::lock_guard<std::mutex> io_lk(dg->io_mu);
-            HostIO &io = dg->io;
-            if (!io.stream) HIP_TRY(hipStreamCreateWithFlags(io.stream.put(), hipStreamNonBlocking));
-            if ((size_t)nb > io.cap_frames) {
-                int r;
-                if ((r = io.llr.alloc(nb * n)) || (r = io.post.alloc(nb * n)) || (r = io.synd.alloc(nb * m)) ||
-                    (r = io.bits.alloc(nb * n)) || (r = io.ok.alloc((size_t)nb)) || (r = io.iters.alloc((size_t)nb)))
-                    return r;
-                io.cap_frames = (size_t)nb;
-            }
+    const size_t n = (size_t)g->n, m = (size_t)g->m;
+    return for_each_shard(
+        g, batch, "a host-only graph cannot decode", [&](DeviceGraph *dg, HostIO &io, int f0, int nb) -> int {
+            if (int r = io.reserve((size_t)nb, n, m, true, true, false)) return r;
             // the shard's trace arrays, for this call alone (allocated before anything is enqueued)
             const size_t rows = (size_t)nb * (size_t)p->max_iterations;
             DevBuf<uint32_t> d_unsat;
@@ -1061,25 +1126,7 @@ static int decode_batch_host(qldpc_graph *g, const qldpc_params *p, int32_t batc
                                        hipMemcpyDeviceToHost, io.stream));
             HIP_TRY(hipStreamSynchronize(io.stream));
             return split_check(g, dg, io.stream);
-        };
-        const int r = body();
-        rcs[gi] = r;
-        if (r) errs[gi] = g_last_error;
-    };
-    {
-        DeviceScope restore;
-        if ((rc = restore.save())) return rc;
-        if (G == 1) {
-            work(0);
-        } else {
-            std::vector<std::thread> th;
-            for (int gi = 0; gi < G; ++gi) th.emplace_back(work, gi);
-            for (auto &t : th) t.join();
-        }
-    }
-    for (int gi = 0; gi < G; ++gi)
-        if (rcs[gi]) return fail(rcs[gi], errs[gi]);
-    return QLDPC_OK;
+        });
 }
 
 int qldpc_decode_batch(qldpc_graph *g, const qldpc_params *p, int32_t batch, const double *llr,
@@ -1217,8 +1264,8 @@ int qldpc_rate_plan_create(qldpc_graph *g, int32_t n_punct, const int32_t *punct
     auto plan = std::make_unique<qldpc_rate_plan>();
     plan->n_punct = n_punct;
     plan->n_short = n_short;
-    DeviceScope restore;
-    if (int rc = restore.save()) return rc;
+    DeviceScope restore;  // (a host-only graph: the plan lives on no device, and none is touched)
+    if (int rc = g->devs.empty() ? QLDPC_OK : restore.save()) return rc;
     for (auto &dg : g->devs) {
         HIP_TRY(hipSetDevice(dg->device));
         qldpc_rate_plan::Dev d;
@@ -1327,6 +1374,169 @@ int qldpc_qkd_ldpc_rate_adapt_batch_device(qldpc_graph *g, const qldpc_rate_plan
     return qkd_ldpc_window(g, dg, plan, p, batch, d_alice, d_bob, d_punct_alice, d_punct_bob, d_log_p, d_alice_ext,
                            d_llr_ws, d_synd_ws, d_bits_out, d_iters_out, d_synd_ok_out, d_keys_match_out,
                            (hipStream_t)stream);
+}
+
+// ---- two parties: Alice's syndromes, Bob's decode from his own key ---------------
+// Argument checks, in this order wherever the step applies: NULL graph, the
+// parameters, batch < 0, batch == 0 (OK), NULL buffers (and the plan the
+// extract entry needs), the plan on the device, the device, the LDS fit.
+// Through batch == 0 no device is touched.
+static bool fill_missing(const qldpc_rate_plan *plan, const uint8_t *fill) {
+    return plan && plan->n_punct > 0 && !fill;
+}
+
+int qldpc_syndrome_batch_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t batch,
+                                const uint8_t *d_key, const uint8_t *d_punct_fill, uint8_t *d_key_ext_out,
+                                uint8_t *d_syndrome_out, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!d_key || !d_syndrome_out || fill_missing(plan, d_punct_fill)) return fail(QLDPC_EINVAL, "NULL device buffer");
+    const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, device) : nullptr;
+    if (plan && !pd) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    DeviceGraph *dg = find_dev(g, device);
+    if (!dg) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    if (int r = party_fits(g, true, plan ? plan->n_punct : -1)) return r;
+    DeviceScope ds;
+    if (int r = ds.enter(device)) return r;
+    const hipError_t e = launch_alice_syndrome(g->n, g->m, dg->ell_col.get(), dg->row_deg.get(),
+                                               pd ? pd->cls.get() : nullptr, pd ? pd->src.get() : nullptr,
+                                               plan ? plan->n_punct : 0, batch, d_key, d_punct_fill, d_key_ext_out,
+                                               d_syndrome_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "alice_syndrome");
+    return QLDPC_OK;
+}
+
+int qldpc_reconcile_batch_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, const qldpc_params *p,
+                                 int32_t batch, const uint8_t *d_key, const double *d_log_p,
+                                 const uint8_t *d_syndrome, double *d_llr_ws, uint8_t *d_bits_out,
+                                 uint32_t *d_iters_out, uint8_t *d_synd_ok_out, double *d_posterior_out,
+                                 void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!d_key || !d_log_p || !d_syndrome || !d_bits_out || !d_iters_out || !d_synd_ok_out)
+        return fail(QLDPC_EINVAL, "NULL device buffer");
+    const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, device) : nullptr;
+    if (plan && !pd) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    DeviceGraph *dg = find_dev(g, device);
+    if (!dg) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    if ((rc = party_fits(g, false, -1))) return rc;
+    DeviceScope ds;
+    if ((rc = ds.enter(device))) return rc;
+    return reconcile_window(g, dg, pd, p, batch, d_key, d_log_p, d_syndrome, d_llr_ws, d_bits_out, d_iters_out,
+                            d_synd_ok_out, d_posterior_out, (hipStream_t)stream);
+}
+
+int qldpc_extract_key_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t batch,
+                             const uint8_t *d_bits, uint8_t *d_key_out, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!plan) return fail(QLDPC_EINVAL, "plan is NULL");
+    if (!d_bits || !d_key_out) return fail(QLDPC_EINVAL, "NULL device buffer");
+    const qldpc_rate_plan::Dev *pd = plan_dev(plan, device);
+    if (!pd) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    if (!find_dev(g, device)) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    DeviceScope ds;
+    if (int r = ds.enter(device)) return r;
+    const hipError_t e = launch_extract_key(g->n, g->n - plan->n_punct - plan->n_short, pd->cls.get(), pd->src.get(),
+                                            batch, d_bits, d_key_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "extract_key");
+    return QLDPC_OK;
+}
+
+// The host entries need the plan on every device of the graph (each shard reads its own replica).
+static int plan_on_every_device(const qldpc_graph *g, const qldpc_rate_plan *plan) {
+    if (!plan) return QLDPC_OK;
+    for (auto &dg : g->devs)
+        if (!plan_dev(plan, dg->device)) return fail(QLDPC_EINVAL, "rate plan does not live on every device of the graph");
+    return QLDPC_OK;
+}
+
+int qldpc_syndrome_batch(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t batch, const uint8_t *key,
+                         const uint8_t *punct_fill, uint8_t *key_ext_out, uint8_t *syndrome_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!key || !syndrome_out || fill_missing(plan, punct_fill)) return fail(QLDPC_EINVAL, "NULL host buffer");
+    int rc = plan_on_every_device(g, plan);
+    if (rc) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot compute syndromes on a device");
+    if ((rc = party_fits(g, true, plan ? plan->n_punct : -1))) return rc;
+    const size_t n = (size_t)g->n, m = (size_t)g->m, np = plan ? (size_t)plan->n_punct : 0;
+    return for_each_shard(
+        g, batch, "a host-only graph cannot compute syndromes on a device",
+        [&](DeviceGraph *dg, HostIO &io, int f0, int nb) -> int {
+            if (int r = io.reserve((size_t)nb, n, m, false, false, true)) return r;
+            const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, dg->device) : nullptr;
+            // Alice's fill and her extended key, for this call alone (allocated before anything is enqueued)
+            DevBuf<uint8_t> d_fill, d_ext;
+            if (int r = np ? d_fill.alloc((size_t)nb * np) : QLDPC_OK) return r;
+            if (int r = (plan && key_ext_out) ? d_ext.alloc((size_t)nb * n) : QLDPC_OK) return r;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(io.key.get(), key + f0 * n, nb * n, hipMemcpyHostToDevice, io.stream));
+                if (np)
+                    HIP_TRY(hipMemcpyAsync(d_fill.get(), punct_fill + f0 * np, nb * np, hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(launch_alice_syndrome(g->n, g->m, dg->ell_col.get(), dg->row_deg.get(),
+                                              pd ? pd->cls.get() : nullptr, pd ? pd->src.get() : nullptr, (int)np, nb,
+                                              io.key.get(), d_fill.get(), d_ext.get(), io.synd.get(), io.stream));
+                HIP_TRY(hipMemcpyAsync(syndrome_out + f0 * m, io.synd.get(), nb * m, hipMemcpyDeviceToHost, io.stream));
+                if (plan && key_ext_out)  // (no plan: the key is the frame, nothing is written)
+                    HIP_TRY(hipMemcpyAsync(key_ext_out + f0 * n, d_ext.get(), nb * n, hipMemcpyDeviceToHost, io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t e = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (e != hipSuccess) return hip_fail(e, "syndrome_batch");
+            return QLDPC_OK;
+        });
+}
+
+int qldpc_reconcile_batch(qldpc_graph *g, const qldpc_rate_plan *plan, const qldpc_params *p, int32_t batch,
+                          const uint8_t *key, const double *log_p, const uint8_t *syndrome, uint8_t *bits_out,
+                          uint32_t *iters_out, uint8_t *synd_ok_out, double *posterior_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!key || !log_p || !syndrome || !bits_out || !iters_out || !synd_ok_out)
+        return fail(QLDPC_EINVAL, "NULL host buffer");
+    if ((rc = plan_on_every_device(g, plan))) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot decode");
+    if ((rc = party_fits(g, false, -1))) return rc;
+    const size_t n = (size_t)g->n, m = (size_t)g->m;
+    return for_each_shard(
+        g, batch, "a host-only graph cannot decode", [&](DeviceGraph *dg, HostIO &io, int f0, int nb) -> int {
+            if (int r = io.reserve((size_t)nb, n, m, false, true, true)) return r;
+            const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, dg->device) : nullptr;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(io.key.get(), key + f0 * n, nb * n, hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(hipMemcpyAsync(io.logp.get(), log_p + f0, nb * sizeof(double), hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(hipMemcpyAsync(io.synd.get(), syndrome + f0 * m, nb * m, hipMemcpyHostToDevice, io.stream));
+                if (int r = reconcile_window(g, dg, pd, p, nb, io.key.get(), io.logp.get(), io.synd.get(), nullptr,
+                                             io.bits.get(), io.iters.get(), io.ok.get(),
+                                             posterior_out ? io.post.get() : nullptr, io.stream))
+                    return r;
+                HIP_TRY(hipMemcpyAsync(bits_out + f0 * n, io.bits.get(), nb * n, hipMemcpyDeviceToHost, io.stream));
+                HIP_TRY(hipMemcpyAsync(iters_out + f0, io.iters.get(), nb * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                       io.stream));
+                HIP_TRY(hipMemcpyAsync(synd_ok_out + f0, io.ok.get(), nb, hipMemcpyDeviceToHost, io.stream));
+                if (posterior_out)
+                    HIP_TRY(hipMemcpyAsync(posterior_out + f0 * n, io.post.get(), nb * n * sizeof(double),
+                                           hipMemcpyDeviceToHost, io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t e = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (e != hipSuccess) return hip_fail(e, "reconcile_batch");
+            return split_check(g, dg, io.stream);
+        });
 }
 
 // ---- trial generator (src/simulation.cpp:540-551,713-719,743) ----------------

@@ -238,6 +238,14 @@ inline size_t build_frames_ra_lds(int n, int n_punct) {
     return (2 * (size_t)((n + 31) / 32) + (size_t)((n_punct + 31) / 32) + 2 * (size_t)((n + 63) / 64)) *
            sizeof(uint32_t);
 }
+// ... and of the per-party kernels (parties.hip): Alice's key (+ her punctured
+// fill and the extended key, with a plan) for the syndrome; Bob's key alone.
+inline size_t alice_syndrome_lds(int n, int n_punct /* < 0: no plan */) {
+    const size_t nw = (size_t)((n + 31) / 32);
+    if (n_punct < 0) return nw * sizeof(uint32_t);
+    return (nw + (size_t)((n_punct + 31) / 32) + 2 * (size_t)((n + 63) / 64)) * sizeof(uint32_t);
+}
+inline size_t bob_frames_lds(int n) { return (size_t)((n + 31) / 32) * sizeof(uint32_t); }
 // Threads per frame of the one-workgroup-per-frame byte kernels (frame build,
 // claim weight, key compare): 256, or 1024 for frames of >= 32768 bits, whose
 // batches (C4: 128 frames) leave most CUs idle at 4 waves per frame.
@@ -316,6 +324,20 @@ hipError_t launch_build_frames_ra(int n, int m, const int32_t *ell_col, const in
                                   const uint8_t *palice, const uint8_t *pbob, const double *log_p, uint8_t *alice_ext,
                                   double *llr, uint8_t *synd, uint8_t *codes, double *palette, uint8_t *pal_ok,
                                   const int32_t *col_orig, hipStream_t stream);
+// ---- the per-party cut of the frame builders (parties.hip) --------------------
+// Alice: the syndrome of her (extended) key.  cls == NULL: no plan, the key is
+// the frame; else key_ext (nullable) receives the extended key as bytes.
+hipError_t launch_alice_syndrome(int n, int m, const int32_t *ell_col, const int32_t *row_deg, const uint8_t *cls,
+                                 const int32_t *src, int n_punct, int batch, const uint8_t *key,
+                                 const uint8_t *fill, uint8_t *key_ext, uint8_t *synd, hipStream_t stream);
+// Bob: the f64 LLRs (llr, nullable) and / or the V2 palette form (codes,
+// nullable; with palette and pal_ok) of his key, as the fused builders write them.
+hipError_t launch_bob_frames(int n, const uint8_t *cls, const int32_t *src, int batch, const uint8_t *key,
+                             const double *log_p, double *llr, uint8_t *codes, double *palette, uint8_t *pal_ok,
+                             const int32_t *col_orig, hipStream_t stream);
+// The inverse of the extension: out[f][src[i]] = bits[f][i] where cls[i] == 0.
+hipError_t launch_extract_key(int n, int n_key, const uint8_t *cls, const int32_t *src, int batch,
+                              const uint8_t *bits, uint8_t *out, hipStream_t stream);
 // Claim order of a batch: frames by ascending weight of the channel decision's
 // syndrome mismatch (order.hip).  llr is read only for frames without codes.
 size_t frame_weight_lds(int n);

@@ -161,12 +161,44 @@ struct Workspace {  // per (device, stream): frame counter + decoder scratch
     bool ev_recorded = false;
 };
 
-struct HostIO {  // device staging buffers of the host-buffer entry
+struct HostIO {  // device staging buffers of the host-buffer entries
     DevBuf<double> llr, post;
     DevBuf<uint8_t> synd, bits, ok;
     DevBuf<uint32_t> iters;
-    size_t cap_frames = 0;
+    // the per-party entries' inputs: a party's key bytes and Bob's log_p
+    DevBuf<uint8_t> key;
+    DevBuf<double> logp;
+    // capacities in frames, one per group an entry may do without: the LLRs
+    // (qldpc_decode_batch alone), the decode results, the syndromes, the keys
+    size_t cap_frames = 0, cap_out = 0, cap_synd = 0, cap_key = 0;
     Stream stream;
+    // Grow the groups a call stages (the caller holds io_mu; nothing of an
+    // earlier call is in flight: each entry ends with a stream sync).
+    int reserve(size_t nb, size_t n, size_t m, bool want_llr, bool want_out, bool want_key) {
+        int r;
+        if (want_llr && nb > cap_frames) {
+            cap_frames = 0;
+            if ((r = llr.alloc(nb * n))) return r;
+            cap_frames = nb;
+        }
+        if (want_out && nb > cap_out) {
+            cap_out = 0;
+            if ((r = post.alloc(nb * n)) || (r = bits.alloc(nb * n)) || (r = ok.alloc(nb)) || (r = iters.alloc(nb)))
+                return r;
+            cap_out = nb;
+        }
+        if (nb > cap_synd) {
+            cap_synd = 0;
+            if ((r = synd.alloc(nb * m))) return r;
+            cap_synd = nb;
+        }
+        if (want_key && nb > cap_key) {
+            cap_key = 0;
+            if ((r = key.alloc(nb * n)) || (r = logp.alloc(nb))) return r;
+            cap_key = nb;
+        }
+        return QLDPC_OK;
+    }
 };
 
 // qldpc_run_trials: one pipeline slot of a device's trial batches — the

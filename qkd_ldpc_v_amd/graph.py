@@ -320,6 +320,90 @@ class Graph:
               "qldpc_decode_trace_batch")
         return TraceOutput(bits, iters, ok, post, unsat, tpost)
 
+    # ---- two parties, host buffers (synchronous, shard like decode) ----
+    def _host_keys(self, keys, plan):
+        """A party's key bytes as [batch, n] rows.  With a plan a row's first
+        n_key = n - punctured - shortened entries are the key; rows of exactly
+        n_key entries are accepted and padded."""
+        k = np.ascontiguousarray(keys, np.uint8)
+        if k.ndim == 1:
+            k = k[None, :]
+        if plan is not None and k.ndim == 2 and k.shape[1] == plan.n_key != self.n:
+            k = np.concatenate([k, np.zeros((k.shape[0], self.n - plan.n_key), np.uint8)], axis=1)
+        if k.ndim != 2 or k.shape[1] != self.n:
+            raise ValueError(f"expected keys (batch,{self.n})" + (f" or (batch,{plan.n_key})" if plan is not None else ""))
+        return k, k.shape[0]
+
+    def syndrome(self, keys: np.ndarray, plan: "RatePlan | None" = None, punct_fill: np.ndarray | None = None):
+        """Alice's side (qldpc_syndrome_batch): the syndromes of her keys, uint8
+        [batch, m].  With a plan: (extended keys uint8 [batch, n], syndromes of
+        the extended keys); punct_fill uint8 [batch, n_punct] is her private
+        randomness at the punctured positions."""
+        k, batch = self._host_keys(keys, plan)
+        npun = 0 if plan is None else int(plan.punctured.size)
+        fill = None
+        if npun:
+            if punct_fill is None:
+                raise ValueError(f"the plan punctures {npun} positions: pass punct_fill (batch,{npun})")
+            fill = np.ascontiguousarray(punct_fill, np.uint8).reshape(-1, npun)
+            if fill.shape[0] != batch:
+                raise ValueError(f"expected punct_fill ({batch},{npun})")
+        syn = np.empty((batch, self.m), np.uint8)
+        ext = np.empty((batch, self.n), np.uint8) if plan is not None else None
+        check(lib().qldpc_syndrome_batch(self._g, None if plan is None else plan.handle, batch, ptr(k), ptr(fill),
+                                         ptr(ext), ptr(syn)), "qldpc_syndrome_batch")
+        return syn if plan is None else (ext, syn)
+
+    def reconcile(self, params: Params, keys: np.ndarray, log_p, syndrome: np.ndarray,
+                  plan: "RatePlan | None" = None, posterior: bool = False) -> DecodeOutput:
+        """Bob's side (qldpc_reconcile_batch): decode from his own keys, log_p
+        (one value, or one per frame) and the received syndromes.  With a plan,
+        bits are the extended frames: extract_key maps them back to key bits."""
+        k, batch = self._host_keys(keys, plan)
+        syn = np.ascontiguousarray(syndrome, np.uint8)
+        if syn.ndim == 1:
+            syn = syn[None, :]
+        if syn.shape != (batch, self.m):
+            raise ValueError(f"expected syndrome ({batch},{self.m})")
+        lp = np.ascontiguousarray(np.broadcast_to(np.asarray(log_p, np.float64), (batch,)))
+        bits = np.empty((batch, self.n), np.uint8)
+        iters = np.empty(batch, np.uint32)
+        ok = np.empty(batch, np.uint8)
+        post = np.empty((batch, self.n), np.float64) if posterior else None
+        p = params.c()
+        check(lib().qldpc_reconcile_batch(self._g, None if plan is None else plan.handle, ctypes.byref(p), batch,
+                                          ptr(k), ptr(lp), ptr(syn), ptr(bits), ptr(iters), ptr(ok), ptr(post)),
+              "qldpc_reconcile_batch")
+        return DecodeOutput(bits, iters, ok, post)
+
+    # ---- two parties, device pointers ----
+    def syndrome_device(self, key, syndrome, plan: "RatePlan | None" = None, punct_fill=None, key_ext=None,
+                        stream=None, device: int | None = None) -> None:
+        """Alice: syndrome [batch, m] of key [batch, n] (with a plan: of the
+        extended key, written to key_ext [batch, n] when given)."""
+        dev = key.device.index if device is None else device
+        check(lib().qldpc_syndrome_batch_device(
+            self._g, None if plan is None else plan.handle, dev, int(key.shape[0]), _dp(key), _dp(punct_fill),
+            _dp(key_ext), _dp(syndrome), _stream_ptr(stream, dev)), "qldpc_syndrome_batch_device")
+
+    def reconcile_device(self, params: Params, key, log_p, syndrome, bits, iters, ok, plan: "RatePlan | None" = None,
+                         llr_ws=None, posterior=None, stream=None, device: int | None = None) -> None:
+        """Bob: frames from key [batch, n] and log_p [batch], decoded against the
+        received syndrome [batch, m] (read only)."""
+        dev = key.device.index if device is None else device
+        p = params.c()
+        check(lib().qldpc_reconcile_batch_device(
+            self._g, None if plan is None else plan.handle, dev, ctypes.byref(p), int(key.shape[0]), _dp(key),
+            _dp(log_p), _dp(syndrome), _dp(llr_ws), _dp(bits), _dp(iters), _dp(ok), _dp(posterior),
+            _stream_ptr(stream, dev)), "qldpc_reconcile_batch_device")
+
+    def extract_key_device(self, plan: "RatePlan", bits, key_out, stream=None, device: int | None = None) -> None:
+        """key_out [batch, n_key] = bits [batch, n] at the plan's key positions."""
+        dev = bits.device.index if device is None else device
+        check(lib().qldpc_extract_key_device(self._g, None if plan is None else plan.handle, dev, int(bits.shape[0]),
+                                             _dp(bits), _dp(key_out), _stream_ptr(stream, dev)),
+              "qldpc_extract_key_device")
+
     # ---- device-pointer entries (torch tensors as plumbing) ----
     def decode_device(self, params: Params, llr, syndrome, bits, iters, ok, posterior=None, stream=None,
                       device: int | None = None) -> None:
@@ -430,6 +514,7 @@ class RatePlan:
                                            self.shortened.size, self.shortened.ctypes.data, ctypes.byref(h)),
               "qldpc_rate_plan_create")
         self.handle = h
+        self.n_key = graph.n - int(self.punctured.size) - int(self.shortened.size)  # key bits per frame
         self._graph = graph  # keep the graph alive
 
     def __del__(self):
