@@ -491,6 +491,75 @@ int qldpc_reconcile_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullabl
                           uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
                           double *posterior_out /* nullable */);
 
+/* ---- Blind reconciliation: disclosure rounds for frames that failed -------------
+ * A frame whose decode ended with syndromes_match == 0 need not be lost, nor
+ * the batch be sent again under another rate plan: in blind reconciliation
+ * (Martinez-Mateo, Elkouss, Martin, arXiv:1205.5729) Alice discloses the values
+ * of some of her punctured bits, Bob pins those positions and decodes the failed
+ * frames again, until they decode or nothing is left to disclose.  No round
+ * needs a new syndrome or a new plan; the failed-frame list and the disclosed
+ * bits are all that crosses the channel.  Every disclosed bit is a leaked bit.
+ *
+ * qldpc_failed_frames_device: d_list_out[0 .. count) = the frames f with
+ * d_synd_ok[f] == 0, ASCENDING (both parties index the round by this order),
+ * and *d_count_out = count.  d_list_out holds `batch` entries; those past the
+ * count are unspecified.  The caller reads the count (four bytes) between
+ * rounds: n_list below is a host integer.
+ *
+ * qldpc_disclose_device (Alice): d_vals_out[j][i] = d_punct_fill[d_list[j]][d_disc[i]]
+ * for j < n_list, i < n_disc.  d_disc holds indices k into the plan's ascending
+ * punctured list, the k that index d_punct_fill ([batch][n_punct], the buffer
+ * qldpc_syndrome_batch_device read).
+ *
+ * qldpc_reconcile_round_device (Bob): decodes the frames d_list[0 .. n_list) of
+ * the batch again.  For each, the LLRs are exactly qldpc_reconcile_batch_device's
+ * (+-log_p[f], 1e-4, DBL_MAX), except that the punctured position of index
+ * d_disc[i] holds d_vals[j][i] ? -DBL_MAX : +DBL_MAX (bit 0 of the byte; the
+ * builder's sign).  The frames are decoded from these LLRs like
+ * qldpc_decode_batch_device's, on every graph layout: a disclosed -DBL_MAX has
+ * no code in the register kernels' 2-bit palette, so a round never takes the
+ * palette path that qldpc_reconcile_batch_device takes.  Results go to rows
+ * d_list[j] of the [batch] outputs — iterations_num and syndromes_match of this
+ * round's decode; rows that are not listed are not written, the posterior's
+ * included.  n_disc == 0 is a plain re-decode of the listed frames.  The
+ * compact frames live in the (device, stream) workspace.
+ *
+ * The caller's contract, which the device entries cannot check without a
+ * synchronisation: d_list entries are distinct and in [0, batch); d_disc
+ * entries are distinct and in [0, n_punct).  (Results are unspecified
+ * otherwise.)  The host entries do check both.
+ *
+ * qldpc_disclose_batch / qldpc_reconcile_round_batch: the same on HOST buffers
+ * and a host list, synchronous; contiguous slices of the LIST are sharded over
+ * the graph's devices.  Only the listed frames' fill rows, or key rows, log_p,
+ * syndromes and disclosed bytes, cross to the device.
+ *
+ * A plan is required (without punctured bits there is nothing to disclose).
+ * Arguments are checked in the two-party order: NULL graph, the parameters,
+ * batch < 0, n_list outside [0, batch], n_disc outside [0, n_punct],
+ * n_list == 0 (OK; batch == 0 for the list entry), NULL plan and buffers, the
+ * plan on the device, the device, the LDS fit.  Through n_list == 0 no device
+ * is touched. */
+int qldpc_failed_frames_device(int32_t batch, const uint8_t *d_synd_ok, int32_t *d_list_out /* batch */,
+                               int32_t *d_count_out, void *stream);
+int qldpc_disclose_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t n_list,
+                          const int32_t *d_list, const uint8_t *d_punct_fill /* [batch][n_punct] */, int32_t n_disc,
+                          const int32_t *d_disc, uint8_t *d_vals_out /* [n_list][n_disc] */, void *stream);
+int qldpc_reconcile_round_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, const qldpc_params *p,
+                                 int32_t batch, const uint8_t *d_key, const double *d_log_p,
+                                 const uint8_t *d_syndrome, int32_t n_list, const int32_t *d_list, int32_t n_disc,
+                                 const int32_t *d_disc, const uint8_t *d_vals /* [n_list][n_disc] */,
+                                 uint8_t *d_bits_out, uint32_t *d_iters_out, uint8_t *d_synd_ok_out,
+                                 double *d_posterior_out /* nullable */, void *stream);
+int qldpc_disclose_batch(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t batch, int32_t n_list,
+                         const int32_t *list, const uint8_t *punct_fill /* [batch][n_punct] */, int32_t n_disc,
+                         const int32_t *disc, uint8_t *vals_out /* [n_list][n_disc] */);
+int qldpc_reconcile_round_batch(qldpc_graph *g, const qldpc_rate_plan *plan, const qldpc_params *p, int32_t batch,
+                                const uint8_t *key, const double *log_p, const uint8_t *syndrome, int32_t n_list,
+                                const int32_t *list, int32_t n_disc, const int32_t *disc,
+                                const uint8_t *vals /* [n_list][n_disc] */, uint8_t *bits_out, uint32_t *iters_out,
+                                uint8_t *synd_ok_out, double *posterior_out /* nullable */);
+
 /* ---- Simulation-driver helpers ----------------------
  * qldpc_sort_permutation: the order std::sort (libstdc++, not stable) leaves a
  * sequence in when comparing only `keys` — how the reference orders its

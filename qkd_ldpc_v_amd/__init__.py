@@ -8,6 +8,10 @@ Two parties: Alice publishes Graph.syndrome(keys[, plan, punct_fill]); Bob
 decodes with Graph.reconcile(params, keys, log_p, syndrome[, plan]) from his own
 key and the received syndrome (device forms: syndrome_device, reconcile_device,
 extract_key_device).  Neither call sees the other side's key.
+
+Frames that fail are decoded again in disclosure rounds (blind reconciliation):
+blind.blind_reconcile runs the exchange over Graph.failed_frames_device,
+Graph.disclose[_device] (Alice) and Graph.reconcile_round[_device] (Bob).
 """
 from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, TRACE_NONE, Params, QLDPCError,
                    exported_symbols, lib, log_p, version)
@@ -16,11 +20,14 @@ from .graph import (DecodeOutput, Graph, HMatrix, RatePlan, TraceOutput, TrialsO
                     trial_seeds, trials_device, trials_rate_adapt_device, xoshiro_state)
 from .trials import bsc_frames
 from .codes import regular_code
+from . import blind
+from .blind import BlindOutput, blind_efficiency, blind_reconcile
 
 __all__ = [
     "regular_code",
     "ALGORITHM_NAMES", "ANMSA", "AOMSA", "NMSA", "OMSA", "SPA", "SPA_LIN", "Params", "QLDPCError",
     "exported_symbols", "lib", "log_p", "version", "DecodeOutput", "TrialsOutput", "Graph", "HMatrix", "keys_match_device",
     "trial_seeds", "trials_device", "RatePlan", "adapt_code_rate", "trials_rate_adapt_device", "xoshiro_state",
-    "load_matrix", "bsc_frames", "TraceOutput", "TRACE_NONE",
+    "load_matrix", "bsc_frames", "TraceOutput", "TRACE_NONE", "blind", "BlindOutput", "blind_efficiency",
+    "blind_reconcile",
 ]

@@ -120,6 +120,13 @@ _SIGNATURES = {
     "qldpc_extract_key_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _P]),
     "qldpc_syndrome_batch": (_I32, [_P, _P, _I32, _P, _P, _P, _P]),
     "qldpc_reconcile_batch": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "qldpc_failed_frames_device": (_I32, [_I32, _P, _P, _P, _P]),
+    "qldpc_disclose_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _P, _P, _P]),
+    "qldpc_reconcile_round_device": (_I32, [_P, _P, _I32, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _I32, _P,
+                                            _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "qldpc_disclose_batch": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _P, _P]),
+    "qldpc_reconcile_round_batch": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _I32, _P, _I32, _P,
+                                           _P, _P, _P, _P, _P]),
     "qldpc_trials_device": (_I32, [_I32, ctypes.c_double, _I32, _P, ctypes.c_uint64, _P, _P,
                                    ctypes.POINTER(ctypes.c_double), _P]),
     "qldpc_run_trials": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), ctypes.c_double, _I32, _P, ctypes.c_uint64,

@@ -1,0 +1,116 @@
+"""Blind reconciliation (Martinez-Mateo, Elkouss, Martin, arXiv:1205.5729) over
+the two-party entries: frames whose decode failed are decoded again after Alice
+has disclosed some of her punctured bits, round after round, under one rate
+plan and one syndrome.
+
+Per round, Bob -> Alice: the list of frames that failed; Alice -> Bob: the
+values of the next `step` punctured bits of those frames.  Each disclosed bit
+is a leaked bit, which `efficiency` accounts for.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from ._lib import Params
+from .graph import Graph, RatePlan
+
+
+@dataclass
+class BlindOutput:
+    bits: np.ndarray        # uint8[batch, n]  Bob's extended frames after the frame's last round
+    synd_ok: np.ndarray     # uint8[batch]     syndromes_match of the frame's last round
+    rounds: np.ndarray      # int32[batch]     the round the frame decoded in (0: one-shot), or the last round run
+    disclosed: np.ndarray   # int32[batch]     punctured bits Alice disclosed for the frame
+    iterations: np.ndarray  # uint32[batch]    decoder iterations, summed over the frame's rounds
+    efficiency: np.ndarray  # float64[batch]   blind_efficiency of the frame (NaN without q)
+
+
+def h2(q: float) -> float:
+    """The binary entropy, in bits."""
+    if q <= 0.0 or q >= 1.0:
+        return 0.0
+    return -q * math.log2(q) - (1.0 - q) * math.log2(1.0 - q)
+
+
+def blind_efficiency(n: int, m: int, n_punct: int, n_short: int, disclosed, q: float | None):
+    """(m - n_punct + disclosed) / ((n - n_punct - n_short) h2(q)): the bits the
+    exchange revealed about a frame's key (syndrome bits that are not spent on
+    punctured positions, plus the disclosed ones) over the Slepian-Wolf bound
+    for its n - n_punct - n_short key bits.  NaN when q is not given."""
+    d = np.asarray(disclosed, np.float64)
+    if q is None:
+        return np.full(d.shape, np.nan)
+    return (m - n_punct + d) / ((n - n_punct - n_short) * h2(float(q)))
+
+
+def check_order(order, n_punct: int) -> np.ndarray:
+    """`order` as int32 indices into the plan's punctured list; it must be a
+    permutation of range(n_punct) (None: ascending)."""
+    if order is None:
+        return np.arange(n_punct, dtype=np.int32)
+    o = np.asarray(order)
+    if o.ndim != 1 or o.size != n_punct or not np.issubdtype(o.dtype, np.integer) or \
+            not np.array_equal(np.sort(o), np.arange(n_punct)):
+        raise ValueError(f"order must be a permutation of range({n_punct})")
+    return np.ascontiguousarray(o, np.int32)
+
+
+def failed_frames(graph: Graph, synd_ok: np.ndarray) -> np.ndarray:
+    """The frames with synd_ok == 0, ascending, listed on the device."""
+    import torch
+
+    ok = np.ascontiguousarray(synd_ok, np.uint8)
+    if ok.size == 0:
+        return np.empty(0, np.int32)
+    d_ok = torch.from_numpy(ok).cuda()
+    d_list = torch.empty(ok.size, dtype=torch.int32, device="cuda")
+    d_count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    graph.failed_frames_device(d_ok, d_list, d_count)
+    count = int(d_count.cpu()[0])  # (the four bytes Bob reads between rounds)
+    return d_list[:count].cpu().numpy()
+
+
+def blind_reconcile(ga: Graph, plan_a: RatePlan, gb: Graph, plan_b: RatePlan, params: Params, alice: np.ndarray,
+                    bob: np.ndarray, log_p, fill: np.ndarray, step: int, order=None, max_rounds: int | None = None,
+                    q: float | None = None) -> BlindOutput:
+    """The whole exchange for a batch.  Alice (ga, plan_a, her keys and private
+    fill) publishes one syndrome per frame; Bob (gb, plan_b, his keys) decodes
+    (round 0) and then, while frames fail and punctured bits remain, names the
+    failed frames, receives the next `step` bits of `order` for them and decodes
+    them again with every bit received so far pinned.  max_rounds bounds the
+    disclosure rounds (None: until nothing is left to disclose)."""
+    n_punct = int(plan_b.punctured.size)
+    if int(plan_a.punctured.size) != n_punct or not np.array_equal(plan_a.punctured, plan_b.punctured) or \
+            not np.array_equal(plan_a.shortened, plan_b.shortened):
+        raise ValueError("Alice's and Bob's plans differ")
+    if step < 1:
+        raise ValueError("step must be >= 1")
+    order = check_order(order, n_punct)
+    fill = np.ascontiguousarray(fill, np.uint8).reshape(-1, max(n_punct, 1))
+
+    _, syndrome = ga.syndrome(alice, plan_a, fill if n_punct else None)  # Alice -> Bob, once
+    out = gb.reconcile(params, bob, log_p, syndrome, plan=plan_b)
+    batch = out.synd_ok.shape[0]
+    rounds = np.zeros(batch, np.int32)
+    disclosed = np.zeros(batch, np.int32)
+    iterations = out.iterations.astype(np.uint32)
+    known = np.zeros((batch, max(n_punct, 1)), np.uint8)  # Bob's record of the bits he received
+    r = d = 0
+    while d < n_punct and (max_rounds is None or r < max_rounds):
+        failed = failed_frames(gb, out.synd_ok)  # Bob -> Alice
+        if failed.size == 0:
+            break
+        r += 1
+        new = order[d:min(d + step, n_punct)]
+        d += new.size
+        known[np.ix_(failed, new)] = ga.disclose(plan_a, failed, fill, new)  # Alice -> Bob
+        gb.reconcile_round(params, bob, log_p, syndrome, plan_b, failed, order[:d], known[np.ix_(failed, order[:d])],
+                           out=out)  # (rows `failed` of out: this round's decode)
+        iterations[failed] += out.iterations[failed]
+        rounds[failed] = r
+        disclosed[failed] = d
+    eff = blind_efficiency(gb.n, gb.m, n_punct, int(plan_b.shortened.size), disclosed, q)
+    return BlindOutput(out.bits, out.synd_ok, rounds, disclosed, iterations, eff)

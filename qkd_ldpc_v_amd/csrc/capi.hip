@@ -785,6 +785,60 @@ int reconcile_window(qldpc_graph *g, DeviceGraph *dg, const qldpc_rate_plan::Dev
     return decode_on(g, dg, p, batch, llr, d_synd, d_bits_out, d_iters_out, d_synd_ok_out, d_post_out, s, v2);
 }
 
+// The round's frame kernel keeps Bob's key and one byte per punctured index in
+// LDS (decoder.hpp round_frames_lds).
+int round_fits(const qldpc_graph *g, int n_punct) {
+    const size_t lds = round_frames_lds(g->n, n_punct);
+    if (lds <= LDS_MAX_BYTES) return QLDPC_OK;
+    return fail(QLDPC_EUNSUP, "n = " + std::to_string(g->n) + ": the disclosure round's frame kernel keeps the key in " +
+                                  "LDS (" + std::to_string(lds) + " bytes > " + std::to_string(LDS_MAX_BYTES) +
+                                  "); decode such frames through qldpc_decode_batch[_device] with host-built LLRs");
+}
+
+// One disclosure round for the frames d_list[0 .. n_list) of `batch` device-
+// resident frames on `s` (the current device is dg's): their pinned LLRs and
+// syndromes as compact rows in the stream's workspace, the decode of those
+// n_list frames from the LLRs (a pinned -DBL_MAX has no palette code), and the
+// results scattered to rows d_list[j] of the outputs.  d_list == NULL: the
+// frames 0 .. n_list in order (the host entry's staged rows), decoded straight
+// into the outputs.
+int round_window(qldpc_graph *g, DeviceGraph *dg, const qldpc_rate_plan::Dev *pd, int n_punct, const qldpc_params *p,
+                 int batch, const uint8_t *d_key, const double *d_log_p, const uint8_t *d_synd, int n_list,
+                 const int32_t *d_list, int n_disc, const int32_t *d_disc, const uint8_t *d_vals, uint8_t *d_bits_out,
+                 uint32_t *d_iters_out, uint8_t *d_synd_ok_out, double *d_post_out, hipStream_t s) {
+    const size_t n = (size_t)g->n, m = (size_t)g->m, nl = (size_t)n_list;
+    double *llr, *cpost = d_post_out;
+    uint8_t *synd_ws, *cbits = d_bits_out, *cok = d_synd_ok_out;
+    uint32_t *citers = d_iters_out;
+    {
+        std::lock_guard<std::mutex> lk(dg->mu);
+        Workspace *w = workspace(dg, s);
+        if (int r = grow(w->round_frames, nl, s, [&] {
+                int rc;
+                if ((rc = w->round_llr.alloc(nl * n)) || (rc = w->round_synd.alloc(nl * m)) ||
+                    (rc = w->round_bits.alloc(nl * n)) || (rc = w->round_ok.alloc(nl)))
+                    return rc;
+                return w->round_iters.alloc(nl);
+            }))
+            return r;
+        if (d_list && d_post_out)
+            if (int r = grow(w->round_post_frames, nl, s, [&] { return w->round_post.alloc(nl * n); })) return r;
+        llr = w->round_llr.get();
+        synd_ws = w->round_synd.get();
+        if (d_list) {
+            cbits = w->round_bits.get(); citers = w->round_iters.get(); cok = w->round_ok.get();
+            if (d_post_out) cpost = w->round_post.get();
+        }
+    }
+    HIP_TRY(launch_round_frames(g->n, g->m, batch, n_punct, pd->cls.get(), pd->src.get(), n_list, d_list, d_key,
+                                d_log_p, d_synd, n_disc, d_disc, d_vals, llr, synd_ws, s));
+    if (int r = decode_on(g, dg, p, n_list, llr, synd_ws, cbits, citers, cok, cpost, s)) return r;
+    if (d_list)
+        HIP_TRY(launch_round_scatter(g->n, batch, n_list, d_list, cbits, citers, cok, cpost, d_bits_out, d_iters_out,
+                                     d_synd_ok_out, d_post_out, s));
+    return QLDPC_OK;
+}
+
 }  // namespace
 
 // QKD_LDPC's (plan == NULL) or QKD_LDPC_RATE_ADAPT's per-trial window for
@@ -1536,6 +1590,214 @@ int qldpc_reconcile_batch(qldpc_graph *g, const qldpc_rate_plan *plan, const qld
             if (r) return r;
             if (e != hipSuccess) return hip_fail(e, "reconcile_batch");
             return split_check(g, dg, io.stream);
+        });
+}
+
+// ---- blind reconciliation: disclosure rounds for the frames that failed ----------
+// Argument checks, in the two-party order: NULL graph, the parameters,
+// batch < 0, n_list outside [0, batch], n_disc outside [0, n_punct],
+// n_list == 0 (OK), the plan and NULL buffers, the plan on the device, the
+// device, the LDS fit.  Through n_list == 0 no device is touched.
+static int check_round_counts(const qldpc_rate_plan *plan, int32_t batch /* < 0: unknown */, int32_t n_list,
+                              int32_t n_disc) {
+    if (n_list < 0) return fail(QLDPC_EINVAL, "n_list must be >= 0");
+    if (batch >= 0 && n_list > batch) return fail(QLDPC_EINVAL, "n_list must be <= batch");
+    if (n_disc < 0 || (plan && n_disc > plan->n_punct))
+        return fail(QLDPC_EINVAL, "n_disc must be in [0, n_punct]");
+    return QLDPC_OK;
+}
+
+int qldpc_failed_frames_device(int32_t batch, const uint8_t *d_synd_ok, int32_t *d_list_out, int32_t *d_count_out,
+                               void *stream) {
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!d_synd_ok || !d_list_out || !d_count_out) return fail(QLDPC_EINVAL, "NULL device buffer");
+    const hipError_t e = launch_failed_frames(batch, d_synd_ok, d_list_out, d_count_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "failed_frames");
+    return QLDPC_OK;
+}
+
+int qldpc_disclose_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t n_list,
+                          const int32_t *d_list, const uint8_t *d_punct_fill, int32_t n_disc, const int32_t *d_disc,
+                          uint8_t *d_vals_out, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (int rc = check_round_counts(plan, -1, n_list, n_disc)) return rc;
+    if (n_list == 0) return QLDPC_OK;
+    if (!plan) return fail(QLDPC_EINVAL, "plan is NULL");
+    if (!d_list || (n_disc > 0 && (!d_punct_fill || !d_disc || !d_vals_out)))
+        return fail(QLDPC_EINVAL, "NULL device buffer");
+    if (!plan_dev(plan, device)) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    if (!find_dev(g, device)) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    DeviceScope ds;
+    if (int r = ds.enter(device)) return r;
+    const hipError_t e = launch_disclose(plan->n_punct, n_list, d_list, d_punct_fill, n_disc, d_disc, d_vals_out,
+                                         (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "disclose");
+    return QLDPC_OK;
+}
+
+int qldpc_reconcile_round_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, const qldpc_params *p,
+                                 int32_t batch, const uint8_t *d_key, const double *d_log_p,
+                                 const uint8_t *d_syndrome, int32_t n_list, const int32_t *d_list, int32_t n_disc,
+                                 const int32_t *d_disc, const uint8_t *d_vals, uint8_t *d_bits_out,
+                                 uint32_t *d_iters_out, uint8_t *d_synd_ok_out, double *d_posterior_out,
+                                 void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if ((rc = check_round_counts(plan, batch, n_list, n_disc))) return rc;
+    if (n_list == 0) return QLDPC_OK;
+    if (!plan) return fail(QLDPC_EINVAL, "plan is NULL");
+    if (!d_key || !d_log_p || !d_syndrome || !d_list || !d_bits_out || !d_iters_out || !d_synd_ok_out ||
+        (n_disc > 0 && (!d_disc || !d_vals)))
+        return fail(QLDPC_EINVAL, "NULL device buffer");
+    const qldpc_rate_plan::Dev *pd = plan_dev(plan, device);
+    if (!pd) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    DeviceGraph *dg = find_dev(g, device);
+    if (!dg) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    if ((rc = round_fits(g, plan->n_punct))) return rc;
+    DeviceScope ds;
+    if ((rc = ds.enter(device))) return rc;
+    return round_window(g, dg, pd, plan->n_punct, p, batch, d_key, d_log_p, d_syndrome, n_list, d_list, n_disc, d_disc,
+                        d_vals, d_bits_out, d_iters_out, d_synd_ok_out, d_posterior_out, (hipStream_t)stream);
+}
+
+// The host entries see the list and the indices, so they check what the device
+// entries leave to the caller: list entries distinct and in [0, batch), disc in
+// [0, n_punct).
+static int check_host_list(int32_t batch, int32_t n_list, const int32_t *list, int32_t n_punct, int32_t n_disc,
+                           const int32_t *disc) {
+    std::vector<bool> seen((size_t)batch, false);
+    for (int j = 0; j < n_list; ++j) {
+        if (list[j] < 0 || list[j] >= batch) return fail(QLDPC_EINVAL, "list names a frame outside [0, batch)");
+        if (seen[list[j]]) return fail(QLDPC_EINVAL, "list names a frame twice");
+        seen[list[j]] = true;
+    }
+    for (int i = 0; i < n_disc; ++i)
+        if (disc[i] < 0 || disc[i] >= n_punct) return fail(QLDPC_EINVAL, "disc names an index outside [0, n_punct)");
+    return QLDPC_OK;
+}
+
+int qldpc_disclose_batch(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t batch, int32_t n_list,
+                         const int32_t *list, const uint8_t *punct_fill, int32_t n_disc, const int32_t *disc,
+                         uint8_t *vals_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    int rc = check_round_counts(plan, batch, n_list, n_disc);
+    if (rc) return rc;
+    if (n_list == 0) return QLDPC_OK;
+    if (!plan) return fail(QLDPC_EINVAL, "plan is NULL");
+    if (!list || (n_disc > 0 && (!punct_fill || !disc || !vals_out))) return fail(QLDPC_EINVAL, "NULL host buffer");
+    if ((rc = check_host_list(batch, n_list, list, plan->n_punct, n_disc, disc))) return rc;
+    if ((rc = plan_on_every_device(g, plan))) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot disclose on a device");
+    if (n_disc == 0) return QLDPC_OK;
+    const size_t np = (size_t)plan->n_punct, nd = (size_t)n_disc;
+    return for_each_shard(
+        g, n_list, "a host-only graph cannot disclose on a device",
+        [&](DeviceGraph *, HostIO &io, int j0, int nb) -> int {
+            // only the listed frames' fill rows travel
+            std::vector<uint8_t> rows((size_t)nb * np);
+            for (int j = 0; j < nb; ++j)
+                std::memcpy(rows.data() + (size_t)j * np, punct_fill + (size_t)list[j0 + j] * np, np);
+            DevBuf<uint8_t> d_fill, d_vals;
+            DevBuf<int32_t> d_disc;
+            if (int r = d_fill.alloc((size_t)nb * np)) return r;
+            if (int r = d_vals.alloc((size_t)nb * nd)) return r;
+            if (int r = d_disc.alloc(nd)) return r;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(d_fill.get(), rows.data(), rows.size(), hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(hipMemcpyAsync(d_disc.get(), disc, nd * sizeof(int32_t), hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(launch_disclose((int)np, nb, nullptr, d_fill.get(), n_disc, d_disc.get(), d_vals.get(),
+                                        io.stream));
+                HIP_TRY(hipMemcpyAsync(vals_out + (size_t)j0 * nd, d_vals.get(), (size_t)nb * nd,
+                                       hipMemcpyDeviceToHost, io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t e = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (e != hipSuccess) return hip_fail(e, "disclose_batch");
+            return QLDPC_OK;
+        });
+}
+
+int qldpc_reconcile_round_batch(qldpc_graph *g, const qldpc_rate_plan *plan, const qldpc_params *p, int32_t batch,
+                                const uint8_t *key, const double *log_p, const uint8_t *syndrome, int32_t n_list,
+                                const int32_t *list, int32_t n_disc, const int32_t *disc, const uint8_t *vals,
+                                uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out, double *posterior_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if ((rc = check_round_counts(plan, batch, n_list, n_disc))) return rc;
+    if (n_list == 0) return QLDPC_OK;
+    if (!plan) return fail(QLDPC_EINVAL, "plan is NULL");
+    if (!key || !log_p || !syndrome || !list || !bits_out || !iters_out || !synd_ok_out ||
+        (n_disc > 0 && (!disc || !vals)))
+        return fail(QLDPC_EINVAL, "NULL host buffer");
+    if ((rc = check_host_list(batch, n_list, list, plan->n_punct, n_disc, disc))) return rc;
+    if ((rc = plan_on_every_device(g, plan))) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot decode");
+    if ((rc = round_fits(g, plan->n_punct))) return rc;
+    const size_t n = (size_t)g->n, m = (size_t)g->m, nd = (size_t)n_disc;
+    return for_each_shard(
+        g, n_list, "a host-only graph cannot decode", [&](DeviceGraph *dg, HostIO &io, int j0, int nb) -> int {
+            if (int r = io.reserve((size_t)nb, n, m, false, true, true)) return r;
+            const qldpc_rate_plan::Dev *pd = plan_dev(plan, dg->device);
+            // only the listed frames' key rows, log_p, syndromes and disclosed bytes travel
+            std::vector<uint8_t> hkey((size_t)nb * n), hsynd((size_t)nb * m), hbits((size_t)nb * n), hok((size_t)nb);
+            std::vector<double> hlogp((size_t)nb), hpost(posterior_out ? (size_t)nb * n : 0);
+            std::vector<uint32_t> hiters((size_t)nb);
+            for (int j = 0; j < nb; ++j) {
+                const size_t f = (size_t)list[j0 + j];
+                std::memcpy(hkey.data() + (size_t)j * n, key + f * n, n);
+                std::memcpy(hsynd.data() + (size_t)j * m, syndrome + f * m, m);
+                hlogp[j] = log_p[f];
+            }
+            DevBuf<uint8_t> d_vals;
+            DevBuf<int32_t> d_disc;
+            if (int r = nd ? d_vals.alloc((size_t)nb * nd) : QLDPC_OK) return r;
+            if (int r = nd ? d_disc.alloc(nd) : QLDPC_OK) return r;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(io.key.get(), hkey.data(), hkey.size(), hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(hipMemcpyAsync(io.logp.get(), hlogp.data(), nb * sizeof(double), hipMemcpyHostToDevice,
+                                       io.stream));
+                HIP_TRY(hipMemcpyAsync(io.synd.get(), hsynd.data(), hsynd.size(), hipMemcpyHostToDevice, io.stream));
+                if (nd) {
+                    HIP_TRY(hipMemcpyAsync(d_vals.get(), vals + (size_t)j0 * nd, (size_t)nb * nd,
+                                           hipMemcpyHostToDevice, io.stream));
+                    HIP_TRY(hipMemcpyAsync(d_disc.get(), disc, nd * sizeof(int32_t), hipMemcpyHostToDevice,
+                                           io.stream));
+                }
+                if (int r = round_window(g, dg, pd, plan->n_punct, p, nb, io.key.get(), io.logp.get(), io.synd.get(),
+                                         nb, nullptr, n_disc, d_disc.get(), d_vals.get(), io.bits.get(),
+                                         io.iters.get(), io.ok.get(), posterior_out ? io.post.get() : nullptr,
+                                         io.stream))
+                    return r;
+                HIP_TRY(hipMemcpyAsync(hbits.data(), io.bits.get(), hbits.size(), hipMemcpyDeviceToHost, io.stream));
+                HIP_TRY(hipMemcpyAsync(hiters.data(), io.iters.get(), nb * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                       io.stream));
+                HIP_TRY(hipMemcpyAsync(hok.data(), io.ok.get(), nb, hipMemcpyDeviceToHost, io.stream));
+                if (posterior_out)
+                    HIP_TRY(hipMemcpyAsync(hpost.data(), io.post.get(), hpost.size() * sizeof(double),
+                                           hipMemcpyDeviceToHost, io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t e = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (e != hipSuccess) return hip_fail(e, "reconcile_round_batch");
+            if (int sc = split_check(g, dg, io.stream)) return sc;
+            for (int j = 0; j < nb; ++j) {  // (distinct rows: the shards write disjoint frames)
+                const size_t f = (size_t)list[j0 + j];
+                std::memcpy(bits_out + f * n, hbits.data() + (size_t)j * n, n);
+                iters_out[f] = hiters[j];
+                synd_ok_out[f] = hok[j];
+                if (posterior_out) std::memcpy(posterior_out + f * n, hpost.data() + (size_t)j * n, n * sizeof(double));
+            }
+            return QLDPC_OK;
         });
 }
 

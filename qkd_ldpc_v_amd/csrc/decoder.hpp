@@ -338,6 +338,29 @@ hipError_t launch_bob_frames(int n, const uint8_t *cls, const int32_t *src, int 
 // The inverse of the extension: out[f][src[i]] = bits[f][i] where cls[i] == 0.
 hipError_t launch_extract_key(int n, int n_key, const uint8_t *cls, const int32_t *src, int batch,
                               const uint8_t *bits, uint8_t *out, hipStream_t stream);
+// ---- blind reconciliation's disclosure rounds (blind.hip) ------------------------
+// list[0 .. *count) = the frames with synd_ok == 0, ascending (entries past the
+// count are not written).
+hipError_t launch_failed_frames(int batch, const uint8_t *synd_ok, int32_t *list, int32_t *count,
+                                hipStream_t stream);
+// Alice: out[j][i] = fill[list[j]][disc[i]] (list == NULL: frame j).
+hipError_t launch_disclose(int n_punct, int n_list, const int32_t *list, const uint8_t *fill, int n_disc,
+                           const int32_t *disc, uint8_t *out, hipStream_t stream);
+// Bob: compact rows j < n_list of the round's LLRs and syndromes for the frames
+// list[j] (NULL: frame j) of the [batch] inputs: launch_bob_frames' LLRs with the
+// punctured positions of indices disc[i] pinned at vals[j][i] ? -DBL_MAX : DBL_MAX.
+// Dynamic LDS: Bob's key as bit words and one byte per punctured index.
+inline size_t round_frames_lds(int n, int n_punct) {
+    return ((size_t)((n + 31) / 32) + (size_t)((n_punct + 3) / 4)) * sizeof(uint32_t);
+}
+hipError_t launch_round_frames(int n, int m, int batch, int n_punct, const uint8_t *cls, const int32_t *src,
+                               int n_list, const int32_t *list, const uint8_t *key, const double *log_p,
+                               const uint8_t *synd, int n_disc, const int32_t *disc, const uint8_t *vals,
+                               double *llr, uint8_t *synd_ws, hipStream_t stream);
+// Rows list[j] of the [batch] outputs <- compact row j (cpost / post nullable together).
+hipError_t launch_round_scatter(int n, int batch, int n_list, const int32_t *list, const uint8_t *cbits,
+                                const uint32_t *citers, const uint8_t *cok, const double *cpost, uint8_t *bits,
+                                uint32_t *iters, uint8_t *ok, double *post, hipStream_t stream);
 // Claim order of a batch: frames by ascending weight of the channel decision's
 // syndrome mismatch (order.hip).  llr is read only for frames without codes.
 size_t frame_weight_lds(int n);

@@ -149,6 +149,13 @@ struct Workspace {  // per (device, stream): frame counter + decoder scratch
     // graph's decoder reads llr[] (not V2), capacity in frames
     DevBuf<double> llr_ws;
     size_t llr_ws_frames = 0;
+    // a disclosure round's compact frames (qldpc_reconcile_round_device): the
+    // pinned LLRs and syndromes the decoder reads, and its results before the
+    // scatter, capacity in frames; the posteriors only once a caller asks
+    DevBuf<double> round_llr, round_post;
+    DevBuf<uint8_t> round_synd, round_bits, round_ok;
+    DevBuf<uint32_t> round_iters;
+    size_t round_frames = 0, round_post_frames = 0;
     // frame-per-lane tiles (decoder_fpl.hip): messages, totals, LLRs and lane
     // masks of one chunk, capacity in tiles
     DevBuf<uint64_t> fpl;

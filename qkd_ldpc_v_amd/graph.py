@@ -404,6 +404,94 @@ class Graph:
                                              _dp(bits), _dp(key_out), _stream_ptr(stream, dev)),
               "qldpc_extract_key_device")
 
+    # ---- blind reconciliation: disclosure rounds for the frames that failed ----
+    @staticmethod
+    def _round_lists(plan, batch, frames, disc):
+        if plan is None:
+            raise ValueError("a disclosure round needs a rate plan")
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        dc = np.ascontiguousarray([] if disc is None else disc, np.int32).reshape(-1)
+        if fr.size > batch:
+            raise ValueError(f"{fr.size} listed frames of a batch of {batch}")
+        return fr, dc
+
+    def disclose(self, plan: "RatePlan", frames, punct_fill: np.ndarray, disc) -> np.ndarray:
+        """Alice's side of a round (qldpc_disclose_batch): her fill at the
+        punctured indices disc, for the listed frames: uint8 [n_list, n_disc]."""
+        npun = 0 if plan is None else int(plan.punctured.size)
+        fill = np.ascontiguousarray(punct_fill, np.uint8).reshape(-1, max(npun, 1))
+        fr, dc = self._round_lists(plan, fill.shape[0], frames, disc)
+        vals = np.empty((fr.size, dc.size), np.uint8)
+        check(lib().qldpc_disclose_batch(self._g, plan.handle, fill.shape[0], fr.size, ptr(fr), ptr(fill), dc.size,
+                                         ptr(dc), ptr(vals)), "qldpc_disclose_batch")
+        return vals
+
+    def reconcile_round(self, params: Params, keys: np.ndarray, log_p, syndrome: np.ndarray, plan: "RatePlan", frames,
+                        disc, vals, out: DecodeOutput | None = None, posterior: bool = False) -> DecodeOutput:
+        """Bob's side of a round (qldpc_reconcile_round_batch): the listed frames
+        decoded again with the punctured indices disc pinned at vals [n_list,
+        n_disc].  Rows `frames` of `out` (the previous round's output; zeros
+        when not given) receive this round's results, the others are kept."""
+        k, batch = self._host_keys(keys, plan)
+        syn = np.ascontiguousarray(syndrome, np.uint8)
+        if syn.ndim == 1:
+            syn = syn[None, :]
+        if syn.shape != (batch, self.m):
+            raise ValueError(f"expected syndrome ({batch},{self.m})")
+        fr, dc = self._round_lists(plan, batch, frames, disc)
+        v = np.ascontiguousarray(np.empty((fr.size, 0)) if vals is None else vals, np.uint8)
+        if v.size != fr.size * dc.size or (v.ndim == 2 and v.shape != (fr.size, dc.size)):
+            raise ValueError(f"expected vals ({fr.size},{dc.size})")
+        v = v.reshape(fr.size, dc.size)
+        lp = np.ascontiguousarray(np.broadcast_to(np.asarray(log_p, np.float64), (batch,)))
+        if out is None:
+            out = DecodeOutput(np.zeros((batch, self.n), np.uint8), np.zeros(batch, np.uint32), np.zeros(batch, np.uint8),
+                               np.zeros((batch, self.n), np.float64) if posterior else None)
+        want_post = out.posterior is not None
+        shapes = (out.bits.shape == (batch, self.n) and out.iterations.shape == (batch,) and
+                  out.synd_ok.shape == (batch,) and (not want_post or out.posterior.shape == (batch, self.n)))
+        dtypes = (out.bits.dtype == np.uint8 and out.iterations.dtype == np.uint32 and out.synd_ok.dtype == np.uint8 and
+                  (not want_post or out.posterior.dtype == np.float64))
+        if not (shapes and dtypes):
+            raise ValueError(f"out must be a DecodeOutput of {batch} frames")
+        p = params.c()
+        check(lib().qldpc_reconcile_round_batch(
+            self._g, plan.handle, ctypes.byref(p), batch, ptr(k), ptr(lp), ptr(syn), fr.size, ptr(fr), dc.size,
+            ptr(dc), ptr(v), ptr(out.bits), ptr(out.iterations), ptr(out.synd_ok),
+            ptr(out.posterior) if want_post else None), "qldpc_reconcile_round_batch")
+        return out
+
+    def failed_frames_device(self, ok, list_out, count_out, stream=None) -> None:
+        """list_out[:count] = the frames with ok == 0, ascending; count_out[0] =
+        their count (ok uint8 [batch], list_out int32 [batch], count_out int32 [1])."""
+        dev = ok.device.index
+        check(lib().qldpc_failed_frames_device(int(ok.shape[0]), _dp(ok), _dp(list_out), _dp(count_out),
+                                               _stream_ptr(stream, dev)), "qldpc_failed_frames_device")
+
+    def disclose_device(self, plan: "RatePlan", frames, punct_fill, disc, vals_out, n_list: int | None = None,
+                        stream=None, device: int | None = None) -> None:
+        """Alice: vals_out [n_list, n_disc] = punct_fill[frames][:, disc] (int32
+        device lists; n_list: the entries of `frames` in use, all by default)."""
+        dev = punct_fill.device.index if device is None else device
+        check(lib().qldpc_disclose_device(
+            self._g, None if plan is None else plan.handle, dev, int(frames.shape[0]) if n_list is None else int(n_list),
+            _dp(frames), _dp(punct_fill), 0 if disc is None else int(disc.shape[0]), _dp(disc), _dp(vals_out),
+            _stream_ptr(stream, dev)), "qldpc_disclose_device")
+
+    def reconcile_round_device(self, params: Params, key, log_p, syndrome, plan: "RatePlan", frames, disc, vals, bits,
+                               iters, ok, posterior=None, n_list: int | None = None, stream=None,
+                               device: int | None = None) -> None:
+        """Bob: the listed frames of key [batch, n] decoded again with the
+        punctured indices disc pinned at vals [n_list, n_disc]; rows `frames` of
+        bits / iters / ok / posterior ([batch] arrays) receive the results."""
+        dev = key.device.index if device is None else device
+        p = params.c()
+        check(lib().qldpc_reconcile_round_device(
+            self._g, None if plan is None else plan.handle, dev, ctypes.byref(p), int(key.shape[0]), _dp(key),
+            _dp(log_p), _dp(syndrome), int(frames.shape[0]) if n_list is None else int(n_list), _dp(frames),
+            0 if disc is None else int(disc.shape[0]), _dp(disc), _dp(vals), _dp(bits), _dp(iters), _dp(ok),
+            _dp(posterior), _stream_ptr(stream, dev)), "qldpc_reconcile_round_device")
+
     # ---- device-pointer entries (torch tensors as plumbing) ----
     def decode_device(self, params: Params, llr, syndrome, bits, iters, ok, posterior=None, stream=None,
                       device: int | None = None) -> None:
