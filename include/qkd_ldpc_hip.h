@@ -560,6 +560,60 @@ int qldpc_reconcile_round_batch(qldpc_graph *g, const qldpc_rate_plan *plan, con
                                 const uint8_t *vals /* [n_list][n_disc] */, uint8_t *bits_out, uint32_t *iters_out,
                                 uint8_t *synd_ok_out, double *posterior_out /* nullable */);
 
+/* ---- Key verification and privacy amplification: a batched Toeplitz hash ---------
+ * After reconciliation both sides hold key_len bits per frame.  A universal
+ * hash of them closes the protocol twice: a short output (64 bits) is the
+ * verification tag the two sides compare, since syndromes_match alone does not
+ * prove equal keys; a long output, with a length per frame, is privacy
+ * amplification, which takes out what the syndromes and the disclosed bits of
+ * the blind rounds leaked.
+ *
+ * For a frame's key x[0 .. L) (L = key_len), the public seed s[0 .. L + r - 1)
+ * shared by the batch, and r = out_len:
+ *
+ *     y[i] = XOR over j in [0, L) of  s[i + L - 1 - j] & x[j]      for i in [0, r)
+ *
+ * the Toeplitz matrix T[i][j] = s[i - j + L - 1] over GF(2).
+ *
+ * Prefix property: row i reads s[i .. i + L) only, so the first r' outputs of a
+ * hash are the hash for out_len = r' under the seed's first L + r' - 1 entries.
+ * Per-frame output lengths therefore cost nothing: a shorter frame is a prefix
+ * of the same hash.
+ *
+ * All bit arrays are bytes.  Only bit 0 of a key byte or a seed byte is read;
+ * outputs are 0 or 1.
+ *
+ * qldpc_toeplitz_hash_device: d_keys holds `batch` rows, key_stride bytes apart
+ * (>= key_len; bytes of a row past key_len are never part of the result), so
+ * the [batch][n_key] keys of qldpc_extract_key_device, [batch][n] decoded bits
+ * and Alice's [batch][n] key rows of which the first n_key count all pass
+ * unchanged.  d_out is [batch][out_len] and is always written whole: with
+ * d_out_len NULL every frame gets out_len outputs, otherwise frame f keeps its
+ * first d_out_len[f] outputs (a value outside [0, out_len] is clamped into it)
+ * and the rest of its row is 0.  No graph, no workspace, no allocation: it runs
+ * on the current device, asynchronous on `stream`, and nothing outlives the
+ * call.
+ *
+ * qldpc_toeplitz_hash_batch: the same on HOST buffers, synchronous; the
+ * buffers are staged on the current device for the call (QLDPC_ENOMEM when they
+ * do not fit).  It refuses an out_lens entry outside [0, out_len] with
+ * QLDPC_EINVAL.
+ *
+ * Arguments are checked in this order: batch < 0, key_len < 1, out_len < 1,
+ * key_stride < key_len (QLDPC_EINVAL); batch == 0 (QLDPC_OK); NULL keys, seed
+ * or output (QLDPC_EINVAL); the LDS fit — a workgroup keeps the keys of four
+ * frames and its window of the seed in LDS as bit words, which limits key_len
+ * to 261,888 bits (QLDPC_EUNSUP beyond; also for a batch of 2^26 frames
+ * or more, or an out_len of more than 65535 * 1024); the host entry's out_lens.
+ * Through these no device is touched. */
+int qldpc_toeplitz_hash_device(int32_t batch, int32_t key_len, int64_t key_stride, const uint8_t *d_keys,
+                               int32_t out_len, const uint8_t *d_seed /* [key_len + out_len - 1] */,
+                               const int32_t *d_out_len /* nullable, [batch] */,
+                               uint8_t *d_out /* [batch][out_len] */, void *stream);
+int qldpc_toeplitz_hash_batch(int32_t batch, int32_t key_len, int64_t key_stride, const uint8_t *keys,
+                              int32_t out_len, const uint8_t *seed /* [key_len + out_len - 1] */,
+                              const int32_t *out_lens /* nullable, [batch] */, uint8_t *out /* [batch][out_len] */);
+
 /* ---- Simulation-driver helpers ----------------------
  * qldpc_sort_permutation: the order std::sort (libstdc++, not stable) leaves a
  * sequence in when comparing only `keys` — how the reference orders its

@@ -12,15 +12,20 @@ extract_key_device).  Neither call sees the other side's key.
 Frames that fail are decoded again in disclosure rounds (blind reconciliation):
 blind.blind_reconcile runs the exchange over Graph.failed_frames_device,
 Graph.disclose[_device] (Alice) and Graph.reconcile_round[_device] (Bob).
+
+Both sides then hash their keys (toeplitz_hash[_device], a Toeplitz hash over
+GF(2)): privacy.tag / privacy.verified compare a short tag per frame, and
+privacy.amplify shortens the verified frames by what the exchange leaked
+(privacy.leaked_bits, privacy.secret_length).
 """
 from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, TRACE_NONE, Params, QLDPCError,
                    exported_symbols, lib, log_p, version)
 from .graph import (DecodeOutput, Graph, HMatrix, RatePlan, TraceOutput, TrialsOutput, adapt_code_rate, keys_match_device, load_matrix,
-                    select_punctured_untainted,
+                    select_punctured_untainted, toeplitz_hash, toeplitz_hash_device,
                     trial_seeds, trials_device, trials_rate_adapt_device, xoshiro_state)
 from .trials import bsc_frames
 from .codes import regular_code
-from . import blind
+from . import blind, privacy
 from .blind import BlindOutput, blind_efficiency, blind_reconcile
 
 __all__ = [
@@ -29,5 +34,5 @@ __all__ = [
     "exported_symbols", "lib", "log_p", "version", "DecodeOutput", "TrialsOutput", "Graph", "HMatrix", "keys_match_device",
     "trial_seeds", "trials_device", "RatePlan", "adapt_code_rate", "trials_rate_adapt_device", "xoshiro_state",
     "load_matrix", "bsc_frames", "TraceOutput", "TRACE_NONE", "blind", "BlindOutput", "blind_efficiency",
-    "blind_reconcile",
+    "blind_reconcile", "privacy", "toeplitz_hash", "toeplitz_hash_device",
 ]

@@ -35,15 +35,21 @@ def h2(q: float) -> float:
     return -q * math.log2(q) - (1.0 - q) * math.log2(1.0 - q)
 
 
+def leaked_bits(n: int, m: int, n_punct: int, n_short: int, disclosed):
+    """m - n_punct + disclosed: the bits the exchange revealed about a frame's
+    key — syndrome bits that are not spent on punctured positions, plus the
+    punctured bits Alice disclosed.  What privacy amplification must remove."""
+    return (m - n_punct) + np.asarray(disclosed)
+
+
 def blind_efficiency(n: int, m: int, n_punct: int, n_short: int, disclosed, q: float | None):
-    """(m - n_punct + disclosed) / ((n - n_punct - n_short) h2(q)): the bits the
-    exchange revealed about a frame's key (syndrome bits that are not spent on
-    punctured positions, plus the disclosed ones) over the Slepian-Wolf bound
-    for its n - n_punct - n_short key bits.  NaN when q is not given."""
+    """leaked_bits / ((n - n_punct - n_short) h2(q)): the bits the exchange
+    revealed about a frame's key over the Slepian-Wolf bound for its
+    n - n_punct - n_short key bits.  NaN when q is not given."""
     d = np.asarray(disclosed, np.float64)
     if q is None:
         return np.full(d.shape, np.nan)
-    return (m - n_punct + d) / ((n - n_punct - n_short) * h2(float(q)))
+    return leaked_bits(n, m, n_punct, n_short, d) / ((n - n_punct - n_short) * h2(float(q)))
 
 
 def check_order(order, n_punct: int) -> np.ndarray:

@@ -1801,6 +1801,76 @@ int qldpc_reconcile_round_batch(qldpc_graph *g, const qldpc_rate_plan *plan, con
         });
 }
 
+// ---- key verification and privacy amplification: the Toeplitz hash (privacy.hip) ----
+// What both entries check before a device is touched; *done: batch == 0.
+static int check_hash_args(int32_t batch, int32_t key_len, int64_t key_stride, const void *keys, int32_t out_len,
+                           const void *seed, const int32_t *out_lens, bool host_lens, void *out, bool *done) {
+    *done = false;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (key_len < 1 || out_len < 1) return fail(QLDPC_EINVAL, "key_len and out_len must be >= 1");
+    if (key_stride < key_len) return fail(QLDPC_EINVAL, "key_stride must be >= key_len");
+    if (batch == 0) {
+        *done = true;
+        return QLDPC_OK;
+    }
+    if (!keys || !seed || !out) return fail(QLDPC_EINVAL, host_lens ? "NULL host buffer" : "NULL device buffer");
+    const size_t lds = toeplitz_hash_lds(key_len);
+    if (lds > LDS_MAX_BYTES)
+        return fail(QLDPC_EUNSUP, "key_len " + std::to_string(key_len) + ": the keys of a workgroup need " +
+                                      std::to_string(lds) + " bytes of LDS (> " + std::to_string(LDS_MAX_BYTES) + ")");
+    if (!toeplitz_hash_grid_ok(batch, out_len))
+        return fail(QLDPC_EUNSUP, "batch x out_len is beyond one launch's grid");
+    // (no buffer is read before this point; the device entry clamps in the kernel instead)
+    if (host_lens && out_lens)
+        for (int32_t f = 0; f < batch; ++f)
+            if (out_lens[f] < 0 || out_lens[f] > out_len)
+                return fail(QLDPC_EINVAL, "out_lens[" + std::to_string(f) + "] is outside [0, out_len]");
+    return QLDPC_OK;
+}
+
+int qldpc_toeplitz_hash_device(int32_t batch, int32_t key_len, int64_t key_stride, const uint8_t *d_keys,
+                               int32_t out_len, const uint8_t *d_seed, const int32_t *d_out_len, uint8_t *d_out,
+                               void *stream) {
+    bool done;
+    if (int rc = check_hash_args(batch, key_len, key_stride, d_keys, out_len, d_seed, d_out_len, false, d_out, &done))
+        return rc;
+    if (done) return QLDPC_OK;
+    const hipError_t e = launch_toeplitz_hash(batch, key_len, key_stride, d_keys, out_len, d_seed, d_out_len, d_out,
+                                              (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "toeplitz_hash");
+    return QLDPC_OK;
+}
+
+int qldpc_toeplitz_hash_batch(int32_t batch, int32_t key_len, int64_t key_stride, const uint8_t *keys,
+                              int32_t out_len, const uint8_t *seed, const int32_t *out_lens, uint8_t *out) {
+    bool done;
+    if (int rc = check_hash_args(batch, key_len, key_stride, keys, out_len, seed, out_lens, true, out, &done))
+        return rc;
+    if (done) return QLDPC_OK;
+    // staged on the current device for this call (the last row ends at its key_len)
+    const size_t key_bytes = (size_t)(batch - 1) * (size_t)key_stride + (size_t)key_len;
+    const size_t seed_bytes = (size_t)key_len + (size_t)out_len - 1, out_bytes = (size_t)batch * (size_t)out_len;
+    DevBuf<uint8_t> d_keys, d_seed, d_out;
+    DevBuf<int32_t> d_lens;
+    int rc = d_keys.alloc(key_bytes);
+    if (!rc) rc = d_seed.alloc(seed_bytes);
+    if (!rc) rc = d_out.alloc(out_bytes);
+    if (!rc && out_lens) rc = d_lens.alloc((size_t)batch);
+    if (rc) {  // (any other failure, a missing device among them, keeps its own message)
+        if (hipGetLastError() != hipErrorOutOfMemory) return rc;
+        return fail(QLDPC_ENOMEM, "no device memory for " + std::to_string(key_bytes + seed_bytes + out_bytes) +
+                                      " bytes of keys, seed and hash");
+    }
+    HIP_TRY(hipMemcpy(d_keys.get(), keys, key_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_seed.get(), seed, seed_bytes, hipMemcpyHostToDevice));
+    if (out_lens) HIP_TRY(hipMemcpy(d_lens.get(), out_lens, (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice));
+    const hipError_t e = launch_toeplitz_hash(batch, key_len, key_stride, d_keys.get(), out_len, d_seed.get(),
+                                              out_lens ? d_lens.get() : nullptr, d_out.get(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "toeplitz_hash");
+    HIP_TRY(hipMemcpy(out, d_out.get(), out_bytes, hipMemcpyDeviceToHost));  // (after the kernel: the null stream)
+    return QLDPC_OK;
+}
+
 // ---- trial generator (src/simulation.cpp:540-551,713-719,743) ----------------
 int qldpc_xoshiro_jump(uint64_t seed, uint64_t draws, uint64_t *state_out) {
     if (!state_out) return fail(QLDPC_EINVAL, "NULL state_out");

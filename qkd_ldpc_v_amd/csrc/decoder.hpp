@@ -361,6 +361,24 @@ hipError_t launch_round_frames(int n, int m, int batch, int n_punct, const uint8
 hipError_t launch_round_scatter(int n, int batch, int n_list, const int32_t *list, const uint8_t *cbits,
                                 const uint32_t *citers, const uint8_t *cok, const double *cpost, uint8_t *bits,
                                 uint32_t *iters, uint8_t *ok, double *post, hipStream_t stream);
+// ---- key verification and privacy amplification (privacy.hip) ----------------------
+// out[f][i] = XOR_j seed[i + key_len - 1 - j] & keys[f][j] for i < out_lens[f]
+// (NULL: out_len; clamped into [0, out_len]), 0 for the rest of the row.  A
+// workgroup hashes HASH_TILE outputs of HASH_FRAMES frames.  Dynamic LDS: the
+// frames' keys as bit words (rows padded to 4 words) and the tile's seed window.
+constexpr int HASH_THREADS = 256, HASH_TILE = 1024, HASH_FRAMES = 4;
+constexpr int hash_seed_words(int key_len) { return 4 * ((key_len + 127) / 128) + HASH_TILE / 32; }
+inline size_t toeplitz_hash_lds(int key_len) {
+    const size_t kw4 = 4 * (((size_t)key_len + 127) / 128);  // (as hash_seed_words, whatever the key's length)
+    return ((size_t)HASH_FRAMES * kw4 + kw4 + HASH_TILE / 32) * sizeof(uint32_t);
+}
+// The grid is (frame groups, output tiles): HIP bounds x * threads below 2^32 and y by 65535.
+inline bool toeplitz_hash_grid_ok(int batch, int out_len) {
+    return ((long long)batch + HASH_FRAMES - 1) / HASH_FRAMES * HASH_THREADS < (1ll << 32) &&
+           ((long long)out_len + HASH_TILE - 1) / HASH_TILE <= 65535;
+}
+hipError_t launch_toeplitz_hash(int batch, int key_len, long long key_stride, const uint8_t *keys, int out_len,
+                                const uint8_t *seed, const int32_t *out_lens, uint8_t *out, hipStream_t stream);
 // Claim order of a batch: frames by ascending weight of the channel decision's
 // syndrome mismatch (order.hip).  llr is read only for frames without codes.
 size_t frame_weight_lds(int n);

@@ -617,6 +617,55 @@ def keys_match_device(alice, bits, out, stream=None) -> None:
                                         _dp(out), _stream_ptr(stream, dev)), "qldpc_keys_match_device")
 
 
+def _hash_key_len(row_len: int, key_len, seed_size: int, out_len: int) -> int:
+    key_len = row_len if key_len is None else int(key_len)
+    if not 1 <= key_len <= row_len:
+        raise ValueError(f"key_len must be in [1, {row_len}] (the key rows' length)")
+    if out_len < 1:
+        raise ValueError("out_len must be >= 1")
+    if seed_size < key_len + out_len - 1:
+        raise ValueError(f"the seed holds {seed_size} entries; key_len + out_len - 1 = {key_len + out_len - 1} are read")
+    return key_len
+
+
+def toeplitz_hash(keys: np.ndarray, seed: np.ndarray, out_len: int, out_lens=None, key_len: int | None = None):
+    """The Toeplitz hash of every key row (qldpc_toeplitz_hash_batch), host arrays:
+    out[f, i] = XOR_j seed[i + key_len - 1 - j] & keys[f, j], uint8 [batch, out_len].
+    key_len (default: the row length) shorter than the rows hashes each row's
+    first key_len bytes.  out_lens (int [batch], each in [0, out_len]): frame f
+    keeps its first out_lens[f] outputs, the rest of its row is 0."""
+    k = np.ascontiguousarray(keys, np.uint8)
+    if k.ndim == 1:
+        k = k[None, :]
+    s = np.ascontiguousarray(seed, np.uint8).reshape(-1)
+    out_len = int(out_len)
+    key_len = _hash_key_len(k.shape[1], key_len, s.size, out_len)
+    lens = None
+    if out_lens is not None:
+        lens = np.ascontiguousarray(out_lens, np.int32).reshape(-1)
+        if lens.size != k.shape[0]:
+            raise ValueError(f"expected {k.shape[0]} out_lens")
+    out = np.empty((k.shape[0], out_len), np.uint8)
+    check(lib().qldpc_toeplitz_hash_batch(k.shape[0], key_len, k.shape[1], ptr(k), out_len, ptr(s), ptr(lens),
+                                          ptr(out)), "qldpc_toeplitz_hash_batch")
+    return out
+
+
+def toeplitz_hash_device(keys, seed, out, out_lens=None, key_len: int | None = None, stream=None) -> None:
+    """qldpc_toeplitz_hash_device on device tensors: keys uint8 [batch, row],
+    seed uint8 [>= key_len + out_len - 1], out uint8 [batch, out_len], out_lens
+    int32 [batch] or None.  Asynchronous on `stream` (default: the current one)."""
+    dev = keys.device.index
+    key_len = _hash_key_len(int(keys.shape[1]), key_len, int(seed.numel()), int(out.shape[1]))
+    if int(out.shape[0]) != int(keys.shape[0]) or (out_lens is not None and int(out_lens.numel()) != int(keys.shape[0])):
+        raise ValueError(f"out and out_lens must hold {int(keys.shape[0])} frames")
+    if out_lens is not None and str(out_lens.dtype) != "torch.int32":
+        raise ValueError("out_lens must be an int32 tensor")
+    check(lib().qldpc_toeplitz_hash_device(int(keys.shape[0]), key_len, int(keys.shape[1]), _dp(keys),
+                                           int(out.shape[1]), _dp(seed), _dp(out_lens), _dp(out),
+                                           _stream_ptr(stream, dev)), "qldpc_toeplitz_hash_device")
+
+
 def trial_seeds(simulation_seed: int, count: int) -> np.ndarray:
     """Per-trial seeds of the simulation loop (src/simulation.cpp:713-719)."""
     out = np.empty(count, np.uint64)
