@@ -614,6 +614,64 @@ int qldpc_toeplitz_hash_batch(int32_t batch, int32_t key_len, int64_t key_stride
                               int32_t out_len, const uint8_t *seed /* [key_len + out_len - 1] */,
                               const int32_t *out_lens /* nullable, [batch] */, uint8_t *out /* [batch][out_len] */);
 
+/* ---- Block privacy amplification: one Toeplitz hash over many frames ------------
+ * The statistical terms of a finite-key bound fall like 1/sqrt(block length), so
+ * keys are verified and amplified in blocks of 10^6 .. 10^8 bits: hundreds to
+ * thousands of frames hashed as one key.  The block is the concatenation, in
+ * LIST ORDER, of the listed frames' keys,
+ *
+ *     x[t * key_len + j] = d_keys[d_list[t]][j] & 1      t < n_list, j < key_len
+ *
+ * with L = n_list * key_len, and the hash is the formula above, unchanged, with
+ * r = out_len and a seed of L + r - 1 entries:
+ *
+ *     y[i] = XOR over j in [0, L) of  s[i + L - 1 - j] & x[j]      for i in [0, r)
+ *
+ * For a one-frame block it is qldpc_toeplitz_hash_device's row of that frame, bit
+ * for bit, and the prefix property holds as it does there.  The cost is
+ * O(N log N), N the smallest power of two >= L + r - 1: y[i] is bit 0 of entry
+ * i + L - 1 of the integer convolution of s and x, which a number-theoretic
+ * transform of length N modulo the prime 15 * 2^27 + 1 computes exactly (every
+ * entry is a count <= L).  No floating point takes part.  The limit is
+ * L + out_len - 1 <= 2^27 (QLDPC_EUNSUP beyond).
+ *
+ * qldpc_toeplitz_block_workspace: the bytes of workspace a call with this
+ * block length L and out_len needs (two arrays of N words, the table of N
+ * twiddles, 16 bytes of alignment slack), or a negative QLDPC_E*: QLDPC_EINVAL
+ * for block_len < 1 or out_len < 1, QLDPC_EUNSUP beyond the limit.
+ *
+ * qldpc_toeplitz_hash_block_device: d_keys holds rows key_stride bytes apart
+ * (>= key_len), as for qldpc_toeplitz_hash_device.  n_list is a host integer
+ * (the verdicts crossed the channel: both sides know the count); d_list holds
+ * n_list frame indices in any order, repeats allowed, or is NULL for the frames
+ * 0 .. n_list - 1.  That its entries index rows of d_keys is the caller's
+ * contract: the device entry cannot check it.  The call is asynchronous on
+ * `stream`, allocates nothing, and writes only d_out[0 .. out_len) and
+ * d_ws[0 .. ws_bytes).  The twiddle table is rebuilt by every call: the
+ * workspace carries nothing from one call to the next, and what it held before
+ * does not matter.
+ *
+ * qldpc_toeplitz_hash_block: the same on HOST buffers, synchronous.  keys holds
+ * `batch` rows; only the listed rows are staged on the current device, with a
+ * workspace of the call's own (QLDPC_ENOMEM when they do not fit).  It refuses a
+ * list entry outside [0, batch) with QLDPC_EINVAL.
+ *
+ * Arguments are checked in this order: (1) n_list < 0, key_len < 1, out_len < 1,
+ * key_stride < key_len, and for the host entry batch < 0 or n_list > batch
+ * (QLDPC_EINVAL); (2) n_list == 0 (QLDPC_OK, nothing is written); (3) NULL keys,
+ * seed, output or workspace (QLDPC_EINVAL); (4) L + out_len - 1 > 2^27
+ * (QLDPC_EUNSUP); (5) ws_bytes below qldpc_toeplitz_block_workspace(L, out_len)
+ * (QLDPC_EINVAL; qldpc_last_error() names the size needed); (6) the host
+ * entry's list entries.  Through these no device is touched. */
+int64_t qldpc_toeplitz_block_workspace(int64_t block_len, int64_t out_len);
+int qldpc_toeplitz_hash_block_device(int32_t n_list, const int32_t *d_list /* nullable: frames 0..n_list-1 */,
+                                     int32_t key_len, int64_t key_stride, const uint8_t *d_keys, int64_t out_len,
+                                     const uint8_t *d_seed /* [L + out_len - 1] */, uint8_t *d_out /* [out_len] */,
+                                     void *d_ws, int64_t ws_bytes, void *stream);
+int qldpc_toeplitz_hash_block(int32_t batch, int32_t n_list, const int32_t *list /* nullable */, int32_t key_len,
+                              int64_t key_stride, const uint8_t *keys, int64_t out_len,
+                              const uint8_t *seed /* [L + out_len - 1] */, uint8_t *out /* [out_len] */);
+
 /* ---- Simulation-driver helpers ----------------------
  * qldpc_sort_permutation: the order std::sort (libstdc++, not stable) leaves a
  * sequence in when comparing only `keys` — how the reference orders its

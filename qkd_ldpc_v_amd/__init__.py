@@ -16,12 +16,15 @@ Graph.disclose[_device] (Alice) and Graph.reconcile_round[_device] (Bob).
 Both sides then hash their keys (toeplitz_hash[_device], a Toeplitz hash over
 GF(2)): privacy.tag / privacy.verified compare a short tag per frame, and
 privacy.amplify shortens the verified frames by what the exchange leaked
-(privacy.leaked_bits, privacy.secret_length).
+(privacy.leaked_bits, privacy.secret_length).  toeplitz_hash_block[_device]
+hashes the concatenation of a list of frames' keys as one block, up to 2^27
+bits (privacy.block_tag, privacy.block_secret_length, privacy.block_amplify).
 """
 from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, TRACE_NONE, Params, QLDPCError,
                    exported_symbols, lib, log_p, version)
 from .graph import (DecodeOutput, Graph, HMatrix, RatePlan, TraceOutput, TrialsOutput, adapt_code_rate, keys_match_device, load_matrix,
-                    select_punctured_untainted, toeplitz_hash, toeplitz_hash_device,
+                    select_punctured_untainted, toeplitz_block_workspace, toeplitz_hash, toeplitz_hash_block,
+                    toeplitz_hash_block_device, toeplitz_hash_device,
                     trial_seeds, trials_device, trials_rate_adapt_device, xoshiro_state)
 from .trials import bsc_frames
 from .codes import regular_code
@@ -35,4 +38,5 @@ __all__ = [
     "trial_seeds", "trials_device", "RatePlan", "adapt_code_rate", "trials_rate_adapt_device", "xoshiro_state",
     "load_matrix", "bsc_frames", "TraceOutput", "TRACE_NONE", "blind", "BlindOutput", "blind_efficiency",
     "blind_reconcile", "privacy", "toeplitz_hash", "toeplitz_hash_device",
+    "toeplitz_block_workspace", "toeplitz_hash_block", "toeplitz_hash_block_device",
 ]

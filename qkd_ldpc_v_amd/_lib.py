@@ -129,6 +129,10 @@ _SIGNATURES = {
                                            _P, _P, _P, _P, _P]),
     "qldpc_toeplitz_hash_device": (_I32, [_I32, _I32, ctypes.c_int64, _P, _I32, _P, _P, _P, _P]),
     "qldpc_toeplitz_hash_batch": (_I32, [_I32, _I32, ctypes.c_int64, _P, _I32, _P, _P, _P]),
+    "qldpc_toeplitz_block_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "qldpc_toeplitz_hash_block_device": (_I32, [_I32, _P, _I32, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P,
+                                                ctypes.c_int64, _P]),
+    "qldpc_toeplitz_hash_block": (_I32, [_I32, _I32, _P, _I32, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
     "qldpc_trials_device": (_I32, [_I32, ctypes.c_double, _I32, _P, ctypes.c_uint64, _P, _P,
                                    ctypes.POINTER(ctypes.c_double), _P]),
     "qldpc_run_trials": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), ctypes.c_double, _I32, _P, ctypes.c_uint64,

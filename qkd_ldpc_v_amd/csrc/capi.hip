@@ -1871,6 +1871,94 @@ int qldpc_toeplitz_hash_batch(int32_t batch, int32_t key_len, int64_t key_stride
     return QLDPC_OK;
 }
 
+// ---- the hash of one long block (privacy_block.hip) ----
+int64_t qldpc_toeplitz_block_workspace(int64_t block_len, int64_t out_len) {
+    if (block_len < 1 || out_len < 1) return fail(QLDPC_EINVAL, "block_len and out_len must be >= 1");
+    const int k = toeplitz_block_log2(block_len, out_len);
+    if (k < 0) return fail(QLDPC_EUNSUP, "block_len + out_len - 1 is beyond 2^27");
+    return (int64_t)toeplitz_block_ws(k);
+}
+
+// What both entries check before a device is touched (the header's steps 1-5; the host entry brings
+// a batch and no workspace); *done: n_list == 0.  *k_out: the transform's log2 size.
+static int check_block_args(int32_t n_list, int32_t key_len, int64_t key_stride, const void *keys, int64_t out_len,
+                            const void *seed, void *out, const void *ws, int64_t ws_bytes, bool host, int32_t batch,
+                            bool *done, int *k_out) {
+    *done = false;
+    if (n_list < 0) return fail(QLDPC_EINVAL, "n_list must be >= 0");
+    if (key_len < 1 || out_len < 1) return fail(QLDPC_EINVAL, "key_len and out_len must be >= 1");
+    if (key_stride < key_len) return fail(QLDPC_EINVAL, "key_stride must be >= key_len");
+    if (host && (batch < 0 || n_list > batch)) return fail(QLDPC_EINVAL, "batch must be >= 0 and n_list <= batch");
+    if (n_list == 0) {
+        *done = true;
+        return QLDPC_OK;
+    }
+    if (!keys || !seed || !out || (!host && !ws))
+        return fail(QLDPC_EINVAL, host ? "NULL host buffer" : "NULL device buffer");
+    const int64_t L = (int64_t)n_list * key_len;
+    const int k = toeplitz_block_log2(L, out_len);
+    if (k < 0)
+        return fail(QLDPC_EUNSUP, "block of " + std::to_string(L) + " bits and out_len " + std::to_string(out_len) +
+                                      ": block + out_len - 1 is beyond 2^27");
+    if (!host && ws_bytes < (int64_t)toeplitz_block_ws(k))
+        return fail(QLDPC_EINVAL, "the workspace holds " + std::to_string(ws_bytes) + " bytes; " +
+                                      std::to_string(toeplitz_block_ws(k)) + " are needed");
+    *k_out = k;
+    return QLDPC_OK;
+}
+
+int qldpc_toeplitz_hash_block_device(int32_t n_list, const int32_t *d_list, int32_t key_len, int64_t key_stride,
+                                     const uint8_t *d_keys, int64_t out_len, const uint8_t *d_seed, uint8_t *d_out,
+                                     void *d_ws, int64_t ws_bytes, void *stream) {
+    bool done;
+    int k;
+    if (int rc = check_block_args(n_list, key_len, key_stride, d_keys, out_len, d_seed, d_out, d_ws, ws_bytes, false,
+                                  0, &done, &k))
+        return rc;
+    if (done) return QLDPC_OK;
+    const hipError_t e = launch_toeplitz_block(n_list, d_list, key_len, key_stride, d_keys, out_len, d_seed, d_out,
+                                               d_ws, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "toeplitz_hash_block");
+    return QLDPC_OK;
+}
+
+int qldpc_toeplitz_hash_block(int32_t batch, int32_t n_list, const int32_t *list, int32_t key_len, int64_t key_stride,
+                              const uint8_t *keys, int64_t out_len, const uint8_t *seed, uint8_t *out) {
+    bool done;
+    int k;
+    if (int rc = check_block_args(n_list, key_len, key_stride, keys, out_len, seed, out, nullptr, -1, true, batch,
+                                  &done, &k))
+        return rc;
+    if (done) return QLDPC_OK;
+    if (list)
+        for (int32_t t = 0; t < n_list; ++t)
+            if (list[t] < 0 || list[t] >= batch)
+                return fail(QLDPC_EINVAL, "list[" + std::to_string(t) + "] is outside [0, batch)");
+    // only the listed rows travel: the block is gathered here and staged on the current device
+    const size_t kl = (size_t)key_len, L = (size_t)n_list * kl, seed_bytes = L + (size_t)out_len - 1;
+    std::vector<uint8_t> block(L);
+    for (int32_t t = 0; t < n_list; ++t)
+        std::memcpy(block.data() + (size_t)t * kl, keys + (size_t)(list ? list[t] : t) * (size_t)key_stride, kl);
+    DevBuf<uint8_t> d_block, d_seed, d_out, d_ws;
+    int rc = d_block.alloc(L);
+    if (!rc) rc = d_seed.alloc(seed_bytes);
+    if (!rc) rc = d_out.alloc((size_t)out_len);
+    if (!rc) rc = d_ws.alloc(toeplitz_block_ws(k));
+    if (rc) {  // (any other failure, a missing device among them, keeps its own message)
+        if (hipGetLastError() != hipErrorOutOfMemory) return rc;
+        return fail(QLDPC_ENOMEM, "no device memory for " +
+                                      std::to_string(L + seed_bytes + (size_t)out_len + toeplitz_block_ws(k)) +
+                                      " bytes of block, seed, hash and workspace");
+    }
+    HIP_TRY(hipMemcpy(d_block.get(), block.data(), L, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_seed.get(), seed, seed_bytes, hipMemcpyHostToDevice));
+    const hipError_t e = launch_toeplitz_block(n_list, nullptr, key_len, key_len, d_block.get(), out_len, d_seed.get(),
+                                               d_out.get(), d_ws.get(), nullptr);
+    if (e != hipSuccess) return hip_fail(e, "toeplitz_hash_block");
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)out_len, hipMemcpyDeviceToHost));  // (after the kernels: the null stream)
+    return QLDPC_OK;
+}
+
 // ---- trial generator (src/simulation.cpp:540-551,713-719,743) ----------------
 int qldpc_xoshiro_jump(uint64_t seed, uint64_t draws, uint64_t *state_out) {
     if (!state_out) return fail(QLDPC_EINVAL, "NULL state_out");

@@ -379,6 +379,26 @@ inline bool toeplitz_hash_grid_ok(int batch, int out_len) {
 }
 hipError_t launch_toeplitz_hash(int batch, int key_len, long long key_stride, const uint8_t *keys, int out_len,
                                 const uint8_t *seed, const int32_t *out_lens, uint8_t *out, hipStream_t stream);
+// ---- the hash of one long block (privacy_block.hip) --------------------------------
+// out[i] = XOR_j seed[i + L - 1 - j] & x[j] for the block x = rows list[0 .. n_list)
+// (NULL: rows 0 ..) of keys, concatenated, L = n_list * key_len: an exact cyclic
+// convolution of N = 2^k >= L + out_len - 1 points by a number-theoretic transform.
+// The lowest NTT_TILE_LOG stages run on a workgroup's LDS tile, the stages above
+// in strided passes of at most NTT_PASS_STAGES stages.  The workspace holds the
+// two arrays and the twiddle table, N words each, from a 16-byte boundary.
+constexpr int NTT_TILE_LOG = 12, NTT_PASS_STAGES = 7, NTT_MAX_LOG = 27;
+// k, or -1 where L + r - 1 is beyond 2^NTT_MAX_LOG (L, r >= 1)
+inline int toeplitz_block_log2(long long L, long long r) {
+    if (L < 1 || r < 1 || L > (1ll << NTT_MAX_LOG) || r > (1ll << NTT_MAX_LOG) || L + r - 1 > (1ll << NTT_MAX_LOG))
+        return -1;
+    int k = 0;
+    while ((1ll << k) < L + r - 1) ++k;
+    return k;
+}
+inline size_t toeplitz_block_ws(int k) { return 3 * sizeof(uint32_t) * ((size_t)1 << k) + 16; }
+hipError_t launch_toeplitz_block(int n_list, const int32_t *list, int key_len, long long key_stride,
+                                 const uint8_t *keys, long long out_len, const uint8_t *seed, uint8_t *out, void *ws,
+                                 hipStream_t stream);
 // Claim order of a batch: frames by ascending weight of the channel decision's
 // syndrome mismatch (order.hip).  llr is read only for frames without codes.
 size_t frame_weight_lds(int n);

@@ -666,6 +666,92 @@ def toeplitz_hash_device(keys, seed, out, out_lens=None, key_len: int | None = N
                                            _stream_ptr(stream, dev)), "qldpc_toeplitz_hash_device")
 
 
+def toeplitz_block_workspace(block_len: int, out_len: int) -> int:
+    """Bytes of workspace qldpc_toeplitz_hash_block_device needs for a block of
+    block_len bits and out_len outputs (block_len + out_len - 1 <= 2^27)."""
+    need = int(lib().qldpc_toeplitz_block_workspace(int(block_len), int(out_len)))
+    if need < 0:
+        check(need, "qldpc_toeplitz_block_workspace")
+    return need
+
+
+def _block_shape(rows: int, row_len: int, key_len, n_frames, seed_size: int, out_len: int):
+    """-> (key_len, n_list) of a block hash, after the checks of _hash_key_len on the block's length."""
+    key_len = row_len if key_len is None else int(key_len)
+    if not 1 <= key_len <= row_len:
+        raise ValueError(f"key_len must be in [1, {row_len}] (the key rows' length)")
+    n_list = rows if n_frames is None else int(n_frames)
+    if out_len < 1:
+        raise ValueError("out_len must be >= 1")
+    if n_list and seed_size < n_list * key_len + out_len - 1:
+        raise ValueError(f"the seed holds {seed_size} entries; n_list * key_len + out_len - 1 = "
+                         f"{n_list * key_len + out_len - 1} are read")
+    return key_len, n_list
+
+
+def toeplitz_hash_block(keys: np.ndarray, seed: np.ndarray, out_len: int, frames=None, key_len: int | None = None):
+    """The Toeplitz hash of ONE block (qldpc_toeplitz_hash_block), host arrays:
+    the rows keys[frames[0]], keys[frames[1]], ... (None: every row, in order),
+    each cut to key_len, concatenated to L = len(frames) * key_len bits, and
+    out[i] = XOR_j seed[i + L - 1 - j] & block[j], uint8 [out_len].  frames may
+    come in any order and repeat a row, up to as many entries as keys has rows.
+    An empty list hashes nothing: zeros."""
+    k = np.ascontiguousarray(keys, np.uint8)
+    if k.ndim == 1:
+        k = k[None, :]
+    s = np.ascontiguousarray(seed, np.uint8).reshape(-1)
+    out_len = int(out_len)
+    fr = None
+    if frames is not None:
+        fr = np.ascontiguousarray(frames, np.int64).reshape(-1)
+        if fr.size and (int(fr.min()) < 0 or int(fr.max()) >= k.shape[0]):
+            raise ValueError(f"frames must lie in [0, {k.shape[0]})")
+        fr = fr.astype(np.int32)
+    key_len, n_list = _block_shape(k.shape[0], k.shape[1], key_len, None if fr is None else fr.size, s.size, out_len)
+    if n_list > k.shape[0]:
+        raise ValueError(f"frames holds {n_list} entries; the host entry takes at most the {k.shape[0]} rows of keys")
+    out = np.zeros(out_len, np.uint8)
+    check(lib().qldpc_toeplitz_hash_block(k.shape[0], n_list, ptr(fr), key_len, k.shape[1], ptr(k), out_len, ptr(s),
+                                          ptr(out)), "qldpc_toeplitz_hash_block")
+    return out
+
+
+def toeplitz_hash_block_device(keys, seed, out, frames=None, key_len: int | None = None, workspace=None,
+                               stream=None) -> None:
+    """qldpc_toeplitz_hash_block_device on device tensors: keys uint8 [batch, row],
+    seed uint8 [>= L + out_len - 1], out uint8 [out_len], frames int32 [n_list] or
+    None (every row, in order); L = n_list * key_len.  workspace: a uint8 tensor
+    of at least toeplitz_block_workspace(L, out_len) bytes (None: allocated
+    here).  Asynchronous on `stream` (default: the current one); a raw stream
+    handle (an integer, not a torch stream) needs the caller's workspace: one
+    allocated here is freed on return and could not be kept for that stream.
+    That frames index rows of keys is the caller's contract."""
+    dev = keys.device.index
+    if workspace is None and stream is not None and not hasattr(stream, "cuda_stream"):
+        raise ValueError("a raw stream handle needs a workspace: pass workspace=, or a torch stream")
+    if keys.dim() != 2 or out.dim() != 1:
+        raise ValueError("keys must be [batch, row] and out [out_len]")
+    if frames is not None and str(frames.dtype) != "torch.int32":
+        raise ValueError("frames must be an int32 tensor")
+    out_len = int(out.numel())
+    key_len, n_list = _block_shape(int(keys.shape[0]), int(keys.shape[1]), key_len,
+                                   None if frames is None else int(frames.numel()), int(seed.numel()), out_len)
+    if n_list == 0:
+        return
+    if workspace is None:
+        import torch
+
+        workspace = torch.empty(toeplitz_block_workspace(n_list * key_len, out_len), dtype=torch.uint8,
+                                device=keys.device)
+        if stream is not None:  # (freed on return, while the kernels may still run on `stream`)
+            workspace.record_stream(stream)
+    elif str(workspace.dtype) != "torch.uint8":
+        raise ValueError("workspace must be a uint8 tensor")
+    check(lib().qldpc_toeplitz_hash_block_device(n_list, _dp(frames), key_len, int(keys.shape[1]), _dp(keys), out_len,
+                                                 _dp(seed), _dp(out), _dp(workspace), int(workspace.numel()),
+                                                 _stream_ptr(stream, dev)), "qldpc_toeplitz_hash_block_device")
+
+
 def trial_seeds(simulation_seed: int, count: int) -> np.ndarray:
     """Per-trial seeds of the simulation loop (src/simulation.cpp:713-719)."""
     out = np.empty(count, np.uint64)
