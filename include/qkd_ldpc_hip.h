@@ -560,6 +560,96 @@ int qldpc_reconcile_round_batch(qldpc_graph *g, const qldpc_rate_plan *plan, con
                                 const uint8_t *vals /* [n_list][n_disc] */, uint8_t *bits_out, uint32_t *iters_out,
                                 uint8_t *synd_ok_out, double *posterior_out /* nullable */);
 
+/* ---- Symmetric blind reconciliation: disclose each frame's least reliable bits ----
+ * The rounds above disclose punctured bits in one order fixed in advance.  In
+ * symmetric blind reconciliation (Kiktenko, Trushechkin, Lim, Kurochkin,
+ * Fedorov, Phys. Rev. Applied 8, 044017, arXiv:1612.03673) Bob's posteriors of
+ * the failed decode say where the decoder is unsure: he names, per frame, the
+ * `count` positions of smallest |posterior|, Alice answers with her bits there,
+ * and Bob pins those positions and decodes again.  The positions are per FRAME:
+ * d_pos is [batch][cap] int32, row f holding frame f's positions in the order
+ * they were disclosed.  A frame that still fails has been in every round, so
+ * first, count and n_disc are the same for every listed frame.  A plan is
+ * optional: without one every position is a key position.  A disclosed bit is
+ * one leaked bit whatever its class; disclosed key positions stay in the key.
+ *
+ * qldpc_select_positions_device (Bob): for each frame f = d_list[j], j < n_list,
+ * d_pos[f][first .. first + count) = the `count` smallest candidates of row f of
+ * d_posterior ([batch][n]) in the following order, smallest first.  Position i
+ * sorts by the pair (u, i), compared lexicographically, u = the 64 bits of the
+ * posterior with the sign bit cleared, as an unsigned integer: +-0 lowest, then
+ * denormals, normals, +-inf, NaN; equal magnitudes go to the lower index.  The
+ * order is total and uses no floating-point compare, so both numpy and the
+ * device reproduce it bit for bit, and a shorter selection is a prefix of a
+ * longer one.  Candidates are all positions except the plan's shortened ones and
+ * the frame's earlier positions d_pos[f][0 .. first).  Punctured positions are
+ * candidates.  count is at most QLDPC_SELECT_MAX (QLDPC_EUNSUP beyond, nothing is
+ * launched).  Rows of frames that are not listed and columns outside
+ * [first, first + count) are not written.
+ *
+ * qldpc_disclose_positions_device (Alice): d_vals_out[j][i] =
+ * d_ext[f][d_pos[f][first + i]] & 1 for f = d_list[j], i < count.  d_ext is her
+ * extended key (qldpc_syndrome_batch_device's d_key_ext_out) when there is a
+ * plan and her key otherwise, in rows of ext_stride >= n bytes.
+ *
+ * qldpc_reconcile_positions_round_device (Bob): qldpc_reconcile_round_device
+ * with positions.  The LLRs of frame f = d_list[j] are
+ * qldpc_reconcile_batch_device's, then position d_pos[f][i] holds
+ * d_vals[j][i] ? -DBL_MAX : +DBL_MAX for i < n_disc, whatever the position's
+ * class.  d_vals is [n_list][n_disc]: Bob appends each round's answer to his
+ * per-frame history.  Decode, scatter and outputs are the fixed-order round's.
+ *
+ * The caller's contract, which the device entries cannot check without a
+ * synchronisation: d_list entries are distinct and in [0, batch); each listed
+ * frame's d_pos[f][0 .. first) (select), [first, first + count) (disclose) or
+ * [0, n_disc) (round) are distinct and in [0, n); count <= n - n_short - first,
+ * the frame's candidates.  (A position outside [0, n) is skipped, and a count
+ * beyond the candidates leaves -1 in the entries no candidate fills; results are
+ * unspecified otherwise.)  The host entries check all of it (QLDPC_EINVAL).
+ *
+ * The _batch entries: the same on HOST buffers and a host list, synchronous;
+ * contiguous slices of the LIST are sharded over the graph's devices and only
+ * the listed frames' rows cross to the device.
+ *
+ * Arguments are checked in the two-party order: NULL graph, the parameters,
+ * batch < 0, n_list outside [0, batch], first / count / n_disc < 0 or past cap
+ * (first + count <= cap, n_disc <= cap) and ext_stride < n, n_list == 0 (OK),
+ * NULL buffers, the host entries' list and position checks, count >
+ * QLDPC_SELECT_MAX, the plan on the device, the device, the LDS fit
+ * (QLDPC_EUNSUP beyond n of about 850k).  Through n_list == 0 no device is
+ * touched. */
+#define QLDPC_SELECT_MAX 4096 /* positions per frame and call: the winners are sorted in LDS */
+int qldpc_select_positions_device(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t device,
+                                  int32_t batch, const double *d_posterior /* [batch][n] */, int32_t n_list,
+                                  const int32_t *d_list, int32_t first, int32_t count,
+                                  int32_t *d_pos /* [batch][cap] */, int32_t cap, void *stream);
+int qldpc_disclose_positions_device(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t device,
+                                    int32_t n_list, const int32_t *d_list, const uint8_t *d_ext, int64_t ext_stride,
+                                    const int32_t *d_pos /* [batch][cap] */, int32_t cap, int32_t first,
+                                    int32_t count, uint8_t *d_vals_out /* [n_list][count] */, void *stream);
+int qldpc_reconcile_positions_round_device(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t device,
+                                           const qldpc_params *p, int32_t batch, const uint8_t *d_key,
+                                           const double *d_log_p, const uint8_t *d_syndrome, int32_t n_list,
+                                           const int32_t *d_list, int32_t n_disc,
+                                           const int32_t *d_pos /* [batch][cap] */, int32_t cap,
+                                           const uint8_t *d_vals /* [n_list][n_disc] */, uint8_t *d_bits_out,
+                                           uint32_t *d_iters_out, uint8_t *d_synd_ok_out,
+                                           double *d_posterior_out /* nullable */, void *stream);
+int qldpc_select_positions_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t batch,
+                                 const double *posterior /* [batch][n] */, int32_t n_list, const int32_t *list,
+                                 int32_t first, int32_t count, int32_t *pos /* [batch][cap] */, int32_t cap);
+int qldpc_disclose_positions_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t batch,
+                                   int32_t n_list, const int32_t *list, const uint8_t *ext, int64_t ext_stride,
+                                   const int32_t *pos /* [batch][cap] */, int32_t cap, int32_t first, int32_t count,
+                                   uint8_t *vals_out /* [n_list][count] */);
+int qldpc_reconcile_positions_round_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */,
+                                          const qldpc_params *p, int32_t batch, const uint8_t *key,
+                                          const double *log_p, const uint8_t *syndrome, int32_t n_list,
+                                          const int32_t *list, int32_t n_disc, const int32_t *pos /* [batch][cap] */,
+                                          int32_t cap, const uint8_t *vals /* [n_list][n_disc] */, uint8_t *bits_out,
+                                          uint32_t *iters_out, uint8_t *synd_ok_out,
+                                          double *posterior_out /* nullable */);
+
 /* ---- Key verification and privacy amplification: a batched Toeplitz hash ---------
  * After reconciliation both sides hold key_len bits per frame.  A universal
  * hash of them closes the protocol twice: a short output (64 bits) is the

@@ -12,6 +12,9 @@ extract_key_device).  Neither call sees the other side's key.
 Frames that fail are decoded again in disclosure rounds (blind reconciliation):
 blind.blind_reconcile runs the exchange over Graph.failed_frames_device,
 Graph.disclose[_device] (Alice) and Graph.reconcile_round[_device] (Bob).
+blind.symmetric_reconcile discloses each frame's least reliable positions
+instead (Graph.select_positions, disclose_positions, reconcile_positions_round,
+each with a _device form); it needs no rate plan.
 
 Both sides then hash their keys (toeplitz_hash[_device], a Toeplitz hash over
 GF(2)): privacy.tag / privacy.verified compare a short tag per frame, and
@@ -20,7 +23,7 @@ privacy.amplify shortens the verified frames by what the exchange leaked
 hashes the concatenation of a list of frames' keys as one block, up to 2^27
 bits (privacy.block_tag, privacy.block_secret_length, privacy.block_amplify).
 """
-from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, TRACE_NONE, Params, QLDPCError,
+from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, SELECT_MAX, TRACE_NONE, Params, QLDPCError,
                    exported_symbols, lib, log_p, version)
 from .graph import (DecodeOutput, Graph, HMatrix, RatePlan, TraceOutput, TrialsOutput, adapt_code_rate, keys_match_device, load_matrix,
                     select_punctured_untainted, toeplitz_block_workspace, toeplitz_hash, toeplitz_hash_block,
@@ -29,7 +32,7 @@ from .graph import (DecodeOutput, Graph, HMatrix, RatePlan, TraceOutput, TrialsO
 from .trials import bsc_frames
 from .codes import regular_code
 from . import blind, privacy
-from .blind import BlindOutput, blind_efficiency, blind_reconcile
+from .blind import BlindOutput, SymmetricOutput, blind_efficiency, blind_reconcile, symmetric_reconcile
 
 __all__ = [
     "regular_code",
@@ -37,6 +40,6 @@ __all__ = [
     "exported_symbols", "lib", "log_p", "version", "DecodeOutput", "TrialsOutput", "Graph", "HMatrix", "keys_match_device",
     "trial_seeds", "trials_device", "RatePlan", "adapt_code_rate", "trials_rate_adapt_device", "xoshiro_state",
     "load_matrix", "bsc_frames", "TraceOutput", "TRACE_NONE", "blind", "BlindOutput", "blind_efficiency",
-    "blind_reconcile", "privacy", "toeplitz_hash", "toeplitz_hash_device",
+    "blind_reconcile", "SymmetricOutput", "symmetric_reconcile", "SELECT_MAX", "privacy", "toeplitz_hash", "toeplitz_hash_device",
     "toeplitz_block_workspace", "toeplitz_hash_block", "toeplitz_hash_block_device",
 ]

@@ -62,6 +62,7 @@ class qldpc_graph_opts(ctypes.Structure):
 LAYOUT_AUTO, LAYOUT_FRAME_PER_LANE = 0, 1
 LAYOUTS = {"auto": LAYOUT_AUTO, "frame_per_lane": LAYOUT_FRAME_PER_LANE}
 TRACE_NONE = 0xFFFFFFFF  # QLDPC_TRACE_NONE: a trace row that does not exist
+SELECT_MAX = 4096  # QLDPC_SELECT_MAX: positions one select_positions call picks per frame
 
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -127,6 +128,15 @@ _SIGNATURES = {
     "qldpc_disclose_batch": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _P, _P]),
     "qldpc_reconcile_round_batch": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _I32, _P, _I32, _P,
                                            _P, _P, _P, _P, _P]),
+    "qldpc_select_positions_device": (_I32, [_P, _P, _I32, _I32, _P, _I32, _P, _I32, _I32, _P, _I32, _P]),
+    "qldpc_disclose_positions_device": (_I32, [_P, _P, _I32, _I32, _P, _P, ctypes.c_int64, _P, _I32, _I32, _I32, _P,
+                                               _P]),
+    "qldpc_reconcile_positions_round_device": (_I32, [_P, _P, _I32, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P,
+                                                      _I32, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "qldpc_select_positions_batch": (_I32, [_P, _P, _I32, _P, _I32, _P, _I32, _I32, _P, _I32]),
+    "qldpc_disclose_positions_batch": (_I32, [_P, _P, _I32, _I32, _P, _P, ctypes.c_int64, _P, _I32, _I32, _I32, _P]),
+    "qldpc_reconcile_positions_round_batch": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _I32, _P,
+                                                     _I32, _P, _I32, _P, _P, _P, _P, _P]),
     "qldpc_toeplitz_hash_device": (_I32, [_I32, _I32, ctypes.c_int64, _P, _I32, _P, _P, _P, _P]),
     "qldpc_toeplitz_hash_batch": (_I32, [_I32, _I32, ctypes.c_int64, _P, _I32, _P, _P, _P]),
     "qldpc_toeplitz_block_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),

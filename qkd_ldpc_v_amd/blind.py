@@ -28,6 +28,12 @@ class BlindOutput:
     efficiency: np.ndarray  # float64[batch]   blind_efficiency of the frame (NaN without q)
 
 
+@dataclass
+class SymmetricOutput(BlindOutput):
+    """symmetric_reconcile's result: `disclosed` counts positions of any class."""
+    positions: np.ndarray = None  # int32[batch, cap]  the positions disclosed for the frame, in order; -1 past disclosed[f]
+
+
 def h2(q: float) -> float:
     """The binary entropy, in bits."""
     if q <= 0.0 or q >= 1.0:
@@ -120,3 +126,66 @@ def blind_reconcile(ga: Graph, plan_a: RatePlan, gb: Graph, plan_b: RatePlan, pa
         disclosed[failed] = d
     eff = blind_efficiency(gb.n, gb.m, n_punct, int(plan_b.shortened.size), disclosed, q)
     return BlindOutput(out.bits, out.synd_ok, rounds, disclosed, iterations, eff)
+
+
+def symmetric_reconcile(ga: Graph, plan_a: RatePlan | None, gb: Graph, plan_b: RatePlan | None, params: Params,
+                        alice_keys: np.ndarray, bob_keys: np.ndarray, lp, punct_fill: np.ndarray | None = None,
+                        step: int = 20, max_rounds: int | None = None, max_disclosed: int | None = None,
+                        q: float | None = None) -> SymmetricOutput:
+    """Symmetric blind reconciliation (Kiktenko et al., arXiv:1612.03673) for a
+    batch.  Round 0 is Bob's decode against Alice's syndrome, with the posterior
+    kept.  While frames fail, Bob picks for each the `step` candidate positions
+    of smallest |posterior| (select_positions) and names them to Alice with the
+    failed list, Alice answers with her bits there (disclose_positions), and Bob
+    decodes those frames again with every position received so far pinned
+    (reconcile_positions_round).  It ends when nothing fails, after max_rounds
+    disclosure rounds, or at max_disclosed positions per frame (None: every
+    candidate, n - shortened).  The plans may be None on both sides: then every
+    position is a key position and a disclosed bit is a key bit.  Disclosed key
+    positions stay in the key; leaked_bits counts them for privacy amplification."""
+    if (plan_a is None) != (plan_b is None):
+        raise ValueError("Alice's and Bob's plans differ")
+    n_punct = n_short = 0
+    if plan_b is not None:
+        n_punct, n_short = int(plan_b.punctured.size), int(plan_b.shortened.size)
+        if not np.array_equal(plan_a.punctured, plan_b.punctured) or \
+                not np.array_equal(plan_a.shortened, plan_b.shortened):
+            raise ValueError("Alice's and Bob's plans differ")
+    if step < 1:
+        raise ValueError("step must be >= 1")
+    cap = gb.n - n_short if max_disclosed is None else min(int(max_disclosed), gb.n - n_short)
+    if cap < 0:
+        raise ValueError("max_disclosed must be >= 0")
+    if max_rounds is not None:
+        cap = min(cap, step * max(int(max_rounds), 0))
+
+    if plan_a is None:  # Alice -> Bob, once
+        syndrome = ga.syndrome(alice_keys)
+        ext = np.ascontiguousarray(alice_keys, np.uint8).reshape(-1, ga.n)
+    else:
+        fill = None if not n_punct else np.ascontiguousarray(punct_fill, np.uint8).reshape(-1, n_punct)
+        ext, syndrome = ga.syndrome(alice_keys, plan_a, fill)
+    out = gb.reconcile(params, bob_keys, lp, syndrome, plan=plan_b, posterior=True)
+    batch = out.synd_ok.shape[0]
+    rounds = np.zeros(batch, np.int32)
+    disclosed = np.zeros(batch, np.int32)
+    iterations = out.iterations.astype(np.uint32)
+    positions = np.full((batch, max(cap, 1)), -1, np.int32)
+    known = np.zeros((batch, max(cap, 1)), np.uint8)  # Bob's record of the bits he received
+    r = d = 0
+    while d < cap and (max_rounds is None or r < max_rounds):
+        failed = failed_frames(gb, out.synd_ok)
+        if failed.size == 0:
+            break
+        r += 1
+        c = min(step, cap - d)
+        gb.select_positions(out.posterior, failed, d, c, positions, plan=plan_b)  # Bob -> Alice, with the list
+        known[failed, d:d + c] = ga.disclose_positions(ext, failed, positions, d, c, plan=plan_a)  # Alice -> Bob
+        d += c
+        gb.reconcile_positions_round(params, bob_keys, lp, syndrome, failed, d, positions, known[failed, :d],
+                                     plan=plan_b, out=out)  # (rows `failed` of out: this round's decode and posterior)
+        iterations[failed] += out.iterations[failed]
+        rounds[failed] = r
+        disclosed[failed] = d
+    eff = blind_efficiency(gb.n, gb.m, n_punct, n_short, disclosed, q)
+    return SymmetricOutput(out.bits, out.synd_ok, rounds, disclosed, iterations, eff, positions)

@@ -14,6 +14,11 @@
 //     syndromes, for frame list[j] — what bob_frames_kernel writes for that
 //     frame, with the disclosed positions pinned;
 //   - scatter_kernel: the compact decode results back to rows list[j].
+// A symmetric round (arXiv:1612.03673) discloses per-frame positions instead,
+// the ones select.hip picked from Bob's posteriors:
+//   - disclose_positions_kernel (Alice): her bits at the frame's new positions;
+//   - positions_frames_kernel (Bob): round_frames_kernel with the frame's own
+//     position history pinned, of any class, with or without a plan.
 // One workgroup per listed frame where a frame is the unit.  Every global store
 // is a plain vector store.
 #include "decoder_common.hpp"
@@ -139,6 +144,66 @@ __global__ void __launch_bounds__(1024) round_frames_kernel(int n, int m, int ba
     for (int r = threadIdx.x; r < m; r += blockDim.x) sw[r] = s[r];
 }
 
+// Symmetric rounds (select.hip picks the positions): Alice's answer for the
+// positions pos[f][first .. first + count) of frame f = list[j] (NULL: f = j),
+// out[j][i] = ext[f][pos[f][first + i]] & 1.  A position outside [0, n) (the
+// caller's contract) reads nothing and writes 0.
+__global__ void __launch_bounds__(256) disclose_positions_kernel(int n, const int32_t *list, const uint8_t *ext,
+                                                                 size_t ext_stride, const int32_t *pos, int cap,
+                                                                 int first, int count, uint8_t *out) {
+    const size_t j = blockIdx.x, f = list ? (size_t)(uint32_t)list[j] : j;
+    const uint8_t *row = ext + f * ext_stride;
+    const int32_t *p = pos + f * (size_t)cap + first;
+    uint8_t *o = out + j * (size_t)count;
+    for (int i = threadIdx.x; i < count; i += blockDim.x) {
+        const int k = p[i];
+        o[i] = (unsigned)k < (unsigned)n ? (uint8_t)(row[k] & 1u) : (uint8_t)0;
+    }
+}
+
+// round_frames_kernel for a positions round: bob_frames_kernel's values for
+// frame f = list[j] (NULL: f = j), then position pos[f][i] pinned at
+// vals[j][i] ? -DBL_MAX : +DBL_MAX for i < n_disc, whatever its class.  cls ==
+// NULL: no plan.  LDS: Bob's key, the pinned positions and their bits, one bit
+// word array each.
+__global__ void __launch_bounds__(1024) positions_frames_kernel(int n, int m, int batch, const uint8_t *cls,
+                                                               const int32_t *src, const int32_t *list,
+                                                               const uint8_t *key, const double *log_p,
+                                                               const uint8_t *synd, int n_disc, const int32_t *pos,
+                                                               int cap, const uint8_t *vals, double *llr,
+                                                               uint8_t *synd_ws) {
+    extern __shared__ uint32_t kb[];
+    const int nw = (n + 31) / 32;
+    uint32_t *bbits = kb, *pinned = kb + nw, *pinbit = kb + 2 * nw;
+    const size_t j = blockIdx.x, f = list ? (size_t)(uint32_t)list[j] : j;
+    if (f >= (size_t)batch) return;  // (the caller's contract; the whole workgroup leaves)
+    const double lp = log_p[f];
+    dev::pack_key_bits(key + f * (size_t)n, n, bbits);
+    for (int w = threadIdx.x; w < 2 * nw; w += blockDim.x) pinned[w] = 0;
+    __syncthreads();
+    const int32_t *p = pos + f * (size_t)cap;
+    for (int i = threadIdx.x; i < n_disc; i += blockDim.x) {
+        const int k = p[i];
+        if ((unsigned)k < (unsigned)n) {
+            atomicOr(&pinned[k >> 5], 1u << (k & 31));
+            if (vals[j * (size_t)n_disc + i] & 1u) atomicOr(&pinbit[k >> 5], 1u << (k & 31));
+        }
+    }
+    __syncthreads();
+    double *l = llr + j * (size_t)n;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int c = cls ? cls[i] : 0;
+        double v;
+        if (dev::key_bit(pinned, i)) v = dev::key_bit(pinbit, i) ? -PIN : PIN;
+        else if (c == 0) v = dev::key_bit(bbits, cls ? src[i] : i) ? -lp : lp;
+        else v = c == 1 ? 1e-4 : PIN;
+        l[i] = v;
+    }
+    const uint8_t *s = synd + f * (size_t)m;
+    uint8_t *sw = synd_ws + j * (size_t)m;
+    for (int r = threadIdx.x; r < m; r += blockDim.x) sw[r] = s[r];
+}
+
 // Rows list[j] of the caller's arrays <- compact row j of the round's decode.
 __global__ void __launch_bounds__(1024) scatter_kernel(int n, int batch, const int32_t *list, const uint8_t *cbits,
                                                       const uint32_t *citers, const uint8_t *cok, const double *cpost,
@@ -189,6 +254,33 @@ hipError_t launch_round_frames(int n, int m, int batch, int n_punct, const uint8
     }
     hipLaunchKernelGGL(round_frames_kernel, dim3(n_list), dim3(aux_frame_threads(n)), lds, stream, n, m, batch,
                        n_punct, cls, src, list, key, log_p, synd, n_disc, disc, vals, llr, synd_ws);
+    return hipGetLastError();
+}
+
+hipError_t launch_disclose_positions(int n, int n_list, const int32_t *list, const uint8_t *ext, size_t ext_stride,
+                                     const int32_t *pos, int cap, int first, int count, uint8_t *out,
+                                     hipStream_t stream) {
+    if (n_list <= 0 || count <= 0) return hipSuccess;
+    if (first < 0 || (long long)first + count > cap) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(disclose_positions_kernel, dim3(n_list), dim3(256), 0, stream, n, list, ext, ext_stride, pos, cap,
+                       first, count, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_positions_frames(int n, int m, int batch, const uint8_t *cls, const int32_t *src, int n_list,
+                                   const int32_t *list, const uint8_t *key, const double *log_p, const uint8_t *synd,
+                                   int n_disc, const int32_t *pos, int cap, const uint8_t *vals, double *llr,
+                                   uint8_t *synd_ws, hipStream_t stream) {
+    if (n_list <= 0) return hipSuccess;
+    if (n_disc < 0 || n_disc > cap) return hipErrorInvalidValue;
+    const size_t lds = positions_frames_lds(n);
+    if (lds > LDS_MAX_BYTES) return hipErrorInvalidValue;
+    if (lds > 65536) {
+        const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(positions_frames_kernel), lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(positions_frames_kernel, dim3(n_list), dim3(aux_frame_threads(n)), lds, stream, n, m, batch, cls,
+                       src, list, key, log_p, synd, n_disc, pos, cap, vals, llr, synd_ws);
     return hipGetLastError();
 }
 

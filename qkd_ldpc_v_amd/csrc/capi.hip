@@ -801,11 +801,14 @@ int round_fits(const qldpc_graph *g, int n_punct) {
 // n_list frames from the LLRs (a pinned -DBL_MAX has no palette code), and the
 // results scattered to rows d_list[j] of the outputs.  d_list == NULL: the
 // frames 0 .. n_list in order (the host entry's staged rows), decoded straight
-// into the outputs.
+// into the outputs.  by_position: a symmetric round, which pins the frame's
+// own positions d_pos[f][0 .. n_disc) (rows of `cap` entries) instead of the
+// punctured indices d_disc, and needs no plan (pd nullable).
 int round_window(qldpc_graph *g, DeviceGraph *dg, const qldpc_rate_plan::Dev *pd, int n_punct, const qldpc_params *p,
                  int batch, const uint8_t *d_key, const double *d_log_p, const uint8_t *d_synd, int n_list,
                  const int32_t *d_list, int n_disc, const int32_t *d_disc, const uint8_t *d_vals, uint8_t *d_bits_out,
-                 uint32_t *d_iters_out, uint8_t *d_synd_ok_out, double *d_post_out, hipStream_t s) {
+                 uint32_t *d_iters_out, uint8_t *d_synd_ok_out, double *d_post_out, hipStream_t s,
+                 bool by_position = false, const int32_t *d_pos = nullptr, int cap = 0) {
     const size_t n = (size_t)g->n, m = (size_t)g->m, nl = (size_t)n_list;
     double *llr, *cpost = d_post_out;
     uint8_t *synd_ws, *cbits = d_bits_out, *cok = d_synd_ok_out;
@@ -830,8 +833,13 @@ int round_window(qldpc_graph *g, DeviceGraph *dg, const qldpc_rate_plan::Dev *pd
             if (d_post_out) cpost = w->round_post.get();
         }
     }
-    HIP_TRY(launch_round_frames(g->n, g->m, batch, n_punct, pd->cls.get(), pd->src.get(), n_list, d_list, d_key,
-                                d_log_p, d_synd, n_disc, d_disc, d_vals, llr, synd_ws, s));
+    if (by_position)
+        HIP_TRY(launch_positions_frames(g->n, g->m, batch, pd ? pd->cls.get() : nullptr, pd ? pd->src.get() : nullptr,
+                                        n_list, d_list, d_key, d_log_p, d_synd, n_disc, d_pos, cap, d_vals, llr,
+                                        synd_ws, s));
+    else
+        HIP_TRY(launch_round_frames(g->n, g->m, batch, n_punct, pd->cls.get(), pd->src.get(), n_list, d_list, d_key,
+                                    d_log_p, d_synd, n_disc, d_disc, d_vals, llr, synd_ws, s));
     if (int r = decode_on(g, dg, p, n_list, llr, synd_ws, cbits, citers, cok, cpost, s)) return r;
     if (d_list)
         HIP_TRY(launch_round_scatter(g->n, batch, n_list, d_list, cbits, citers, cok, cpost, d_bits_out, d_iters_out,
@@ -1789,6 +1797,320 @@ int qldpc_reconcile_round_batch(qldpc_graph *g, const qldpc_rate_plan *plan, con
             const hipError_t e = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
             if (r) return r;
             if (e != hipSuccess) return hip_fail(e, "reconcile_round_batch");
+            if (int sc = split_check(g, dg, io.stream)) return sc;
+            for (int j = 0; j < nb; ++j) {  // (distinct rows: the shards write disjoint frames)
+                const size_t f = (size_t)list[j0 + j];
+                std::memcpy(bits_out + f * n, hbits.data() + (size_t)j * n, n);
+                iters_out[f] = hiters[j];
+                synd_ok_out[f] = hok[j];
+                if (posterior_out) std::memcpy(posterior_out + f * n, hpost.data() + (size_t)j * n, n * sizeof(double));
+            }
+            return QLDPC_OK;
+        });
+}
+
+// ---- symmetric blind reconciliation: each frame's least reliable positions --------
+// Argument checks, in the two-party order: NULL graph, the parameters,
+// batch < 0, n_list outside [0, batch], first / count / n_disc / cap,
+// n_list == 0 (OK), NULL buffers, (host entries) the list and the position
+// history, count > QLDPC_SELECT_MAX, the plan on the device, the device, the
+// LDS fit.  A plan is optional.  Through n_list == 0 no device is touched.
+static_assert(SELECT_MAX == QLDPC_SELECT_MAX, "the header's limit is the kernel's");
+
+static int check_window(int32_t batch /* < 0: unknown */, int32_t n_list, int32_t first, int32_t count, int32_t cap) {
+    if (n_list < 0) return fail(QLDPC_EINVAL, "n_list must be >= 0");
+    if (batch >= 0 && n_list > batch) return fail(QLDPC_EINVAL, "n_list must be <= batch");
+    if (first < 0 || count < 0 || cap < 0 || (int64_t)first + count > cap)
+        return fail(QLDPC_EINVAL, "first and count must be >= 0 with first + count <= cap");
+    return QLDPC_OK;
+}
+
+static int select_unsupported(int32_t count) {
+    if (count <= QLDPC_SELECT_MAX) return QLDPC_OK;
+    return fail(QLDPC_EUNSUP, "count = " + std::to_string(count) + " exceeds QLDPC_SELECT_MAX (" +
+                                  std::to_string(QLDPC_SELECT_MAX) + "): select in several calls");
+}
+
+static int select_fits(const qldpc_graph *g, int count) {
+    const size_t lds = select_lds(g->n, count);
+    if (lds <= LDS_MAX_BYTES) return QLDPC_OK;
+    return fail(QLDPC_EUNSUP, "n = " + std::to_string(g->n) + ": the select kernel keeps one bit per position in LDS (" +
+                                  std::to_string(lds) + " bytes > " + std::to_string(LDS_MAX_BYTES) + ")");
+}
+
+static int positions_fit(const qldpc_graph *g) {
+    const size_t lds = positions_frames_lds(g->n);
+    if (lds <= LDS_MAX_BYTES) return QLDPC_OK;
+    return fail(QLDPC_EUNSUP, "n = " + std::to_string(g->n) + ": the positions round's frame kernel keeps the key in " +
+                                  "LDS (" + std::to_string(lds) + " bytes > " + std::to_string(LDS_MAX_BYTES) + ")");
+}
+
+int qldpc_select_positions_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t batch,
+                                  const double *d_posterior, int32_t n_list, const int32_t *d_list, int32_t first,
+                                  int32_t count, int32_t *d_pos, int32_t cap, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (int rc = check_window(batch, n_list, first, count, cap)) return rc;
+    if (n_list == 0) return QLDPC_OK;
+    if (!d_list || (count > 0 && (!d_posterior || !d_pos))) return fail(QLDPC_EINVAL, "NULL device buffer");
+    if (int rc = select_unsupported(count)) return rc;
+    const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, device) : nullptr;
+    if (plan && !pd) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    if (!find_dev(g, device)) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    if (int rc = select_fits(g, count)) return rc;
+    DeviceScope ds;
+    if (int r = ds.enter(device)) return r;
+    const hipError_t e = launch_select(g->n, batch, pd ? pd->cls.get() : nullptr, n_list, d_list, d_posterior, first,
+                                       count, d_pos, cap, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "select_positions");
+    return QLDPC_OK;
+}
+
+int qldpc_disclose_positions_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t n_list,
+                                    const int32_t *d_list, const uint8_t *d_ext, int64_t ext_stride,
+                                    const int32_t *d_pos, int32_t cap, int32_t first, int32_t count,
+                                    uint8_t *d_vals_out, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (int rc = check_window(-1, n_list, first, count, cap)) return rc;
+    if (ext_stride < g->n) return fail(QLDPC_EINVAL, "ext_stride must be >= n");
+    if (n_list == 0) return QLDPC_OK;
+    if (!d_list || (count > 0 && (!d_ext || !d_pos || !d_vals_out))) return fail(QLDPC_EINVAL, "NULL device buffer");
+    if (plan && !plan_dev(plan, device)) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    if (!find_dev(g, device)) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    DeviceScope ds;
+    if (int r = ds.enter(device)) return r;
+    const hipError_t e = launch_disclose_positions(g->n, n_list, d_list, d_ext, (size_t)ext_stride, d_pos, cap, first,
+                                                   count, d_vals_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "disclose_positions");
+    return QLDPC_OK;
+}
+
+int qldpc_reconcile_positions_round_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device,
+                                           const qldpc_params *p, int32_t batch, const uint8_t *d_key,
+                                           const double *d_log_p, const uint8_t *d_syndrome, int32_t n_list,
+                                           const int32_t *d_list, int32_t n_disc, const int32_t *d_pos, int32_t cap,
+                                           const uint8_t *d_vals, uint8_t *d_bits_out, uint32_t *d_iters_out,
+                                           uint8_t *d_synd_ok_out, double *d_posterior_out, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if ((rc = check_window(batch, n_list, 0, n_disc, cap))) return rc;
+    if (n_list == 0) return QLDPC_OK;
+    if (!d_key || !d_log_p || !d_syndrome || !d_list || !d_bits_out || !d_iters_out || !d_synd_ok_out ||
+        (n_disc > 0 && (!d_pos || !d_vals)))
+        return fail(QLDPC_EINVAL, "NULL device buffer");
+    const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, device) : nullptr;
+    if (plan && !pd) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    DeviceGraph *dg = find_dev(g, device);
+    if (!dg) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    if ((rc = positions_fit(g))) return rc;
+    DeviceScope ds;
+    if ((rc = ds.enter(device))) return rc;
+    return round_window(g, dg, pd, plan ? plan->n_punct : 0, p, batch, d_key, d_log_p, d_syndrome, n_list, d_list, n_disc,
+                        nullptr, d_vals, d_bits_out, d_iters_out, d_synd_ok_out, d_posterior_out, (hipStream_t)stream,
+                        true, d_pos, cap);
+}
+
+// The host entries see the list and the positions, so they check what the
+// device entries leave to the caller: list entries distinct and in [0, batch);
+// each listed frame's pos[f][0 .. n_hist) distinct and in [0, n); count within
+// the frame's candidates.
+static int check_host_positions(const qldpc_graph *g, const qldpc_rate_plan *plan, int32_t batch, int32_t n_list,
+                                const int32_t *list, const int32_t *pos, int32_t cap, int32_t n_hist,
+                                int32_t count /* < 0: nothing is selected */) {
+    std::vector<bool> seen((size_t)batch, false);
+    for (int j = 0; j < n_list; ++j) {
+        if (list[j] < 0 || list[j] >= batch) return fail(QLDPC_EINVAL, "list names a frame outside [0, batch)");
+        if (seen[list[j]]) return fail(QLDPC_EINVAL, "list names a frame twice");
+        seen[list[j]] = true;
+    }
+    if (count >= 0 && count > g->n - (plan ? plan->n_short : 0) - n_hist)
+        return fail(QLDPC_EINVAL, "count exceeds the frame's candidates (n - n_short - first)");
+    std::vector<int32_t> stamp(n_hist > 0 ? (size_t)g->n : 0, -1);
+    for (int j = 0; j < n_list && n_hist > 0; ++j) {
+        const int32_t *row = pos + (size_t)list[j] * (size_t)cap;
+        for (int i = 0; i < n_hist; ++i) {
+            if (row[i] < 0 || row[i] >= g->n) return fail(QLDPC_EINVAL, "pos names a position outside [0, n)");
+            if (stamp[row[i]] == j) return fail(QLDPC_EINVAL, "pos names a position twice");
+            stamp[row[i]] = j;
+        }
+    }
+    return QLDPC_OK;
+}
+
+int qldpc_select_positions_batch(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t batch, const double *posterior,
+                                 int32_t n_list, const int32_t *list, int32_t first, int32_t count, int32_t *pos,
+                                 int32_t cap) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    int rc = check_window(batch, n_list, first, count, cap);
+    if (rc) return rc;
+    if (n_list == 0) return QLDPC_OK;
+    if (!list || (count > 0 && (!posterior || !pos)) || (first > 0 && !pos)) return fail(QLDPC_EINVAL, "NULL host buffer");
+    if ((rc = check_host_positions(g, plan, batch, n_list, list, pos, cap, first, count))) return rc;
+    if ((rc = select_unsupported(count))) return rc;
+    if ((rc = plan_on_every_device(g, plan))) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot select on a device");
+    if ((rc = select_fits(g, count))) return rc;
+    if (count == 0) return QLDPC_OK;
+    const size_t n = (size_t)g->n, w = (size_t)first + (size_t)count;  // the staged rows hold [0, first + count)
+    return for_each_shard(
+        g, n_list, "a host-only graph cannot select on a device",
+        [&](DeviceGraph *dg, HostIO &io, int j0, int nb) -> int {
+            const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, dg->device) : nullptr;
+            // only the listed frames' posterior rows and position histories travel
+            std::vector<double> hpost((size_t)nb * n);
+            std::vector<int32_t> hpos((size_t)nb * w, -1);
+            for (int j = 0; j < nb; ++j) {
+                const size_t f = (size_t)list[j0 + j];
+                std::memcpy(hpost.data() + (size_t)j * n, posterior + f * n, n * sizeof(double));
+                std::memcpy(hpos.data() + (size_t)j * w, pos + f * (size_t)cap, (size_t)first * sizeof(int32_t));
+            }
+            DevBuf<double> d_post;
+            DevBuf<int32_t> d_pos;
+            if (int r = d_post.alloc((size_t)nb * n)) return r;
+            if (int r = d_pos.alloc((size_t)nb * w)) return r;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(d_post.get(), hpost.data(), hpost.size() * sizeof(double), hipMemcpyHostToDevice,
+                                       io.stream));
+                HIP_TRY(hipMemcpyAsync(d_pos.get(), hpos.data(), hpos.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                                       io.stream));
+                HIP_TRY(launch_select(g->n, nb, pd ? pd->cls.get() : nullptr, nb, nullptr, d_post.get(), first, count,
+                                      d_pos.get(), (int)w, io.stream));
+                HIP_TRY(hipMemcpyAsync(hpos.data(), d_pos.get(), hpos.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                       io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t e = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (e != hipSuccess) return hip_fail(e, "select_positions_batch");
+            for (int j = 0; j < nb; ++j)  // (distinct rows: the shards write disjoint frames)
+                std::memcpy(pos + (size_t)list[j0 + j] * (size_t)cap + first, hpos.data() + (size_t)j * w + first,
+                            (size_t)count * sizeof(int32_t));
+            return QLDPC_OK;
+        });
+}
+
+int qldpc_disclose_positions_batch(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t batch, int32_t n_list,
+                                   const int32_t *list, const uint8_t *ext, int64_t ext_stride, const int32_t *pos,
+                                   int32_t cap, int32_t first, int32_t count, uint8_t *vals_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    int rc = check_window(batch, n_list, first, count, cap);
+    if (rc) return rc;
+    if (ext_stride < g->n) return fail(QLDPC_EINVAL, "ext_stride must be >= n");
+    if (n_list == 0) return QLDPC_OK;
+    if (!list || (count > 0 && (!ext || !pos || !vals_out))) return fail(QLDPC_EINVAL, "NULL host buffer");
+    if ((rc = check_host_positions(g, plan, batch, n_list, list, pos, cap, count > 0 ? first + count : 0, -1))) return rc;
+    if ((rc = plan_on_every_device(g, plan))) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot disclose on a device");
+    if (count == 0) return QLDPC_OK;
+    const size_t n = (size_t)g->n, c = (size_t)count;
+    return for_each_shard(
+        g, n_list, "a host-only graph cannot disclose on a device",
+        [&](DeviceGraph *, HostIO &io, int j0, int nb) -> int {
+            // only the listed frames' rows and new positions travel
+            std::vector<uint8_t> rows((size_t)nb * n);
+            std::vector<int32_t> hpos((size_t)nb * c);
+            for (int j = 0; j < nb; ++j) {
+                const size_t f = (size_t)list[j0 + j];
+                std::memcpy(rows.data() + (size_t)j * n, ext + f * (size_t)ext_stride, n);
+                std::memcpy(hpos.data() + (size_t)j * c, pos + f * (size_t)cap + first, c * sizeof(int32_t));
+            }
+            DevBuf<uint8_t> d_rows, d_vals;
+            DevBuf<int32_t> d_pos;
+            if (int r = d_rows.alloc(rows.size())) return r;
+            if (int r = d_vals.alloc((size_t)nb * c)) return r;
+            if (int r = d_pos.alloc(hpos.size())) return r;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(d_rows.get(), rows.data(), rows.size(), hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(hipMemcpyAsync(d_pos.get(), hpos.data(), hpos.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                                       io.stream));
+                HIP_TRY(launch_disclose_positions(g->n, nb, nullptr, d_rows.get(), n, d_pos.get(), count, 0, count,
+                                                  d_vals.get(), io.stream));
+                HIP_TRY(hipMemcpyAsync(vals_out + (size_t)j0 * c, d_vals.get(), (size_t)nb * c, hipMemcpyDeviceToHost,
+                                       io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t e = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (e != hipSuccess) return hip_fail(e, "disclose_positions_batch");
+            return QLDPC_OK;
+        });
+}
+
+int qldpc_reconcile_positions_round_batch(qldpc_graph *g, const qldpc_rate_plan *plan, const qldpc_params *p,
+                                          int32_t batch, const uint8_t *key, const double *log_p,
+                                          const uint8_t *syndrome, int32_t n_list, const int32_t *list,
+                                          int32_t n_disc, const int32_t *pos, int32_t cap, const uint8_t *vals,
+                                          uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
+                                          double *posterior_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if ((rc = check_window(batch, n_list, 0, n_disc, cap))) return rc;
+    if (n_list == 0) return QLDPC_OK;
+    if (!key || !log_p || !syndrome || !list || !bits_out || !iters_out || !synd_ok_out ||
+        (n_disc > 0 && (!pos || !vals)))
+        return fail(QLDPC_EINVAL, "NULL host buffer");
+    if ((rc = check_host_positions(g, plan, batch, n_list, list, pos, cap, n_disc, -1))) return rc;
+    if ((rc = plan_on_every_device(g, plan))) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot decode");
+    if ((rc = positions_fit(g))) return rc;
+    const size_t n = (size_t)g->n, m = (size_t)g->m, nd = (size_t)n_disc;
+    return for_each_shard(
+        g, n_list, "a host-only graph cannot decode", [&](DeviceGraph *dg, HostIO &io, int j0, int nb) -> int {
+            if (int r = io.reserve((size_t)nb, n, m, false, true, true)) return r;
+            const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, dg->device) : nullptr;
+            // only the listed frames' key rows, log_p, syndromes, positions and disclosed bytes travel
+            std::vector<uint8_t> hkey((size_t)nb * n), hsynd((size_t)nb * m), hbits((size_t)nb * n), hok((size_t)nb);
+            std::vector<double> hlogp((size_t)nb), hpost(posterior_out ? (size_t)nb * n : 0);
+            std::vector<uint32_t> hiters((size_t)nb);
+            std::vector<int32_t> hpos((size_t)nb * nd);
+            for (int j = 0; j < nb; ++j) {
+                const size_t f = (size_t)list[j0 + j];
+                std::memcpy(hkey.data() + (size_t)j * n, key + f * n, n);
+                std::memcpy(hsynd.data() + (size_t)j * m, syndrome + f * m, m);
+                hlogp[j] = log_p[f];
+                if (nd) std::memcpy(hpos.data() + (size_t)j * nd, pos + f * (size_t)cap, nd * sizeof(int32_t));
+            }
+            DevBuf<uint8_t> d_vals;
+            DevBuf<int32_t> d_pos;
+            if (int r = nd ? d_vals.alloc((size_t)nb * nd) : QLDPC_OK) return r;
+            if (int r = nd ? d_pos.alloc(hpos.size()) : QLDPC_OK) return r;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(io.key.get(), hkey.data(), hkey.size(), hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(hipMemcpyAsync(io.logp.get(), hlogp.data(), nb * sizeof(double), hipMemcpyHostToDevice,
+                                       io.stream));
+                HIP_TRY(hipMemcpyAsync(io.synd.get(), hsynd.data(), hsynd.size(), hipMemcpyHostToDevice, io.stream));
+                if (nd) {
+                    HIP_TRY(hipMemcpyAsync(d_pos.get(), hpos.data(), hpos.size() * sizeof(int32_t),
+                                           hipMemcpyHostToDevice, io.stream));
+                    HIP_TRY(hipMemcpyAsync(d_vals.get(), vals + (size_t)j0 * nd, (size_t)nb * nd,
+                                           hipMemcpyHostToDevice, io.stream));
+                }
+                if (int r = round_window(g, dg, pd, plan ? plan->n_punct : 0, p, nb, io.key.get(), io.logp.get(),
+                                         io.synd.get(), nb, nullptr, n_disc, nullptr, d_vals.get(), io.bits.get(),
+                                         io.iters.get(), io.ok.get(), posterior_out ? io.post.get() : nullptr,
+                                         io.stream, true, d_pos.get(), n_disc))
+                    return r;
+                HIP_TRY(hipMemcpyAsync(hbits.data(), io.bits.get(), hbits.size(), hipMemcpyDeviceToHost, io.stream));
+                HIP_TRY(hipMemcpyAsync(hiters.data(), io.iters.get(), nb * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                       io.stream));
+                HIP_TRY(hipMemcpyAsync(hok.data(), io.ok.get(), nb, hipMemcpyDeviceToHost, io.stream));
+                if (posterior_out)
+                    HIP_TRY(hipMemcpyAsync(hpost.data(), io.post.get(), hpost.size() * sizeof(double),
+                                           hipMemcpyDeviceToHost, io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t e = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (e != hipSuccess) return hip_fail(e, "reconcile_positions_round_batch");
             if (int sc = split_check(g, dg, io.stream)) return sc;
             for (int j = 0; j < nb; ++j) {  // (distinct rows: the shards write disjoint frames)
                 const size_t f = (size_t)list[j0 + j];

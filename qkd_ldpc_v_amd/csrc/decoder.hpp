@@ -357,6 +357,27 @@ hipError_t launch_round_frames(int n, int m, int batch, int n_punct, const uint8
                                int n_list, const int32_t *list, const uint8_t *key, const double *log_p,
                                const uint8_t *synd, int n_disc, const int32_t *disc, const uint8_t *vals,
                                double *llr, uint8_t *synd_ws, hipStream_t stream);
+// ---- symmetric blind rounds: per-frame positions (select.hip, blind.hip) --------
+// pos[f][first .. first + count) = the `count` candidate positions of frame
+// f = list[j] (NULL: f = j) with the smallest (|posterior| as 63 bits, index), in
+// that order; candidates are the positions that are neither shortened
+// (cls[i] == 2; cls nullable) nor in pos[f][0 .. first).  pos is [batch][cap].
+constexpr int SELECT_MAX = 4096;  // winners sorted in LDS (QLDPC_SELECT_MAX)
+size_t select_lds(int n, int count);
+hipError_t launch_select(int n, int batch, const uint8_t *cls, int n_list, const int32_t *list, const double *post,
+                         int first, int count, int32_t *pos, int cap, hipStream_t stream);
+// Alice: out[j][i] = ext[f][pos[f][first + i]] & 1 for i < count (ext rows of ext_stride bytes).
+hipError_t launch_disclose_positions(int n, int n_list, const int32_t *list, const uint8_t *ext, size_t ext_stride,
+                                     const int32_t *pos, int cap, int first, int count, uint8_t *out,
+                                     hipStream_t stream);
+// Bob: launch_round_frames with the positions pos[f][0 .. n_disc) pinned at
+// vals[j][i] ? -DBL_MAX : DBL_MAX, whatever their class (cls / src nullable: no plan).
+// Dynamic LDS: the key, the pinned positions and their bits as bit words.
+inline size_t positions_frames_lds(int n) { return 3 * (size_t)((n + 31) / 32) * sizeof(uint32_t); }
+hipError_t launch_positions_frames(int n, int m, int batch, const uint8_t *cls, const int32_t *src, int n_list,
+                                   const int32_t *list, const uint8_t *key, const double *log_p, const uint8_t *synd,
+                                   int n_disc, const int32_t *pos, int cap, const uint8_t *vals, double *llr,
+                                   uint8_t *synd_ws, hipStream_t stream);
 // Rows list[j] of the [batch] outputs <- compact row j (cpost / post nullable together).
 hipError_t launch_round_scatter(int n, int batch, int n_list, const int32_t *list, const uint8_t *cbits,
                                 const uint32_t *citers, const uint8_t *cok, const double *cpost, uint8_t *bits,

@@ -492,6 +492,122 @@ class Graph:
             0 if disc is None else int(disc.shape[0]), _dp(disc), _dp(vals), _dp(bits), _dp(iters), _dp(ok),
             _dp(posterior), _stream_ptr(stream, dev)), "qldpc_reconcile_round_device")
 
+    # ---- symmetric blind reconciliation: per-frame positions (a plan is optional) ----
+    def _positions(self, positions, writable: bool = False):
+        p = positions
+        if not (isinstance(p, np.ndarray) and p.dtype == np.int32 and p.ndim == 2 and p.flags.c_contiguous and
+                (p.flags.writeable or not writable)):
+            raise ValueError("positions must be a C-contiguous int32 array [batch, cap]")
+        return p
+
+    def select_positions(self, posterior: np.ndarray, frames, first: int, count: int, positions: np.ndarray,
+                         plan: "RatePlan | None" = None) -> np.ndarray:
+        """Bob's side of a symmetric round (qldpc_select_positions_batch):
+        positions[f, first:first + count] = the `count` candidates of smallest
+        |posterior| of each listed frame f, in the order (|posterior| as 63 bits,
+        index).  positions is int32 [batch, cap], written in place and returned;
+        its columns before `first` are the frame's earlier positions."""
+        post = np.ascontiguousarray(posterior, np.float64)
+        pos = self._positions(positions, writable=True)
+        if post.ndim != 2 or post.shape[1] != self.n or pos.shape[0] != post.shape[0]:
+            raise ValueError(f"expected posterior (batch,{self.n}) and positions (batch,cap)")
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        check(lib().qldpc_select_positions_batch(self._g, None if plan is None else plan.handle, post.shape[0], ptr(post),
+                                                 fr.size, ptr(fr), int(first), int(count), ptr(pos), pos.shape[1]),
+              "qldpc_select_positions_batch")
+        return pos
+
+    def disclose_positions(self, ext: np.ndarray, frames, positions: np.ndarray, first: int, count: int,
+                           plan: "RatePlan | None" = None) -> np.ndarray:
+        """Alice's side (qldpc_disclose_positions_batch): her bits at
+        positions[f, first:first + count] of the listed frames, uint8 [n_list,
+        count].  ext: her extended keys with a plan, her keys without, in rows
+        of at least n bytes."""
+        e = np.ascontiguousarray(ext, np.uint8)
+        pos = self._positions(positions)
+        if e.ndim != 2 or e.shape[1] < self.n or pos.shape[0] != e.shape[0]:
+            raise ValueError(f"expected ext (batch,>={self.n}) and positions (batch,cap)")
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        vals = np.empty((fr.size, int(count)), np.uint8)
+        check(lib().qldpc_disclose_positions_batch(self._g, None if plan is None else plan.handle, e.shape[0], fr.size,
+                                                   ptr(fr), ptr(e), e.shape[1], ptr(pos), pos.shape[1], int(first),
+                                                   int(count), ptr(vals)), "qldpc_disclose_positions_batch")
+        return vals
+
+    def reconcile_positions_round(self, params: Params, keys: np.ndarray, log_p, syndrome: np.ndarray, frames,
+                                  n_disc: int, positions: np.ndarray, vals, plan: "RatePlan | None" = None,
+                                  out: DecodeOutput | None = None, posterior: bool = False) -> DecodeOutput:
+        """Bob's side (qldpc_reconcile_positions_round_batch): the listed frames
+        decoded again with positions[f, :n_disc] pinned at vals [n_list, n_disc].
+        Rows `frames` of `out` receive this round's results, like reconcile_round."""
+        k, batch = self._host_keys(keys, plan)
+        syn = np.ascontiguousarray(syndrome, np.uint8)
+        if syn.ndim == 1:
+            syn = syn[None, :]
+        if syn.shape != (batch, self.m):
+            raise ValueError(f"expected syndrome ({batch},{self.m})")
+        pos = self._positions(positions)
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        if pos.shape[0] != batch or fr.size > batch:
+            raise ValueError(f"expected positions ({batch},cap) and at most {batch} listed frames")
+        nd = int(n_disc)
+        v = np.ascontiguousarray(np.empty((fr.size, 0)) if vals is None else vals, np.uint8)
+        if v.size != fr.size * nd or (v.ndim == 2 and v.shape != (fr.size, nd)):
+            raise ValueError(f"expected vals ({fr.size},{nd})")
+        v = v.reshape(fr.size, nd)
+        lp = np.ascontiguousarray(np.broadcast_to(np.asarray(log_p, np.float64), (batch,)))
+        if out is None:
+            out = DecodeOutput(np.zeros((batch, self.n), np.uint8), np.zeros(batch, np.uint32), np.zeros(batch, np.uint8),
+                               np.zeros((batch, self.n), np.float64) if posterior else None)
+        want_post = out.posterior is not None
+        shapes = (out.bits.shape == (batch, self.n) and out.iterations.shape == (batch,) and
+                  out.synd_ok.shape == (batch,) and (not want_post or out.posterior.shape == (batch, self.n)))
+        dtypes = (out.bits.dtype == np.uint8 and out.iterations.dtype == np.uint32 and out.synd_ok.dtype == np.uint8 and
+                  (not want_post or out.posterior.dtype == np.float64))
+        if not (shapes and dtypes):
+            raise ValueError(f"out must be a DecodeOutput of {batch} frames")
+        p = params.c()
+        check(lib().qldpc_reconcile_positions_round_batch(
+            self._g, None if plan is None else plan.handle, ctypes.byref(p), batch, ptr(k), ptr(lp), ptr(syn), fr.size,
+            ptr(fr), nd, ptr(pos), pos.shape[1], ptr(v), ptr(out.bits), ptr(out.iterations), ptr(out.synd_ok),
+            ptr(out.posterior) if want_post else None), "qldpc_reconcile_positions_round_batch")
+        return out
+
+    def select_positions_device(self, posterior, frames, first: int, count: int, pos, plan: "RatePlan | None" = None,
+                                n_list: int | None = None, stream=None, device: int | None = None) -> None:
+        """Bob: pos[f, first:first + count] (int32 [batch, cap]) = the listed
+        frames' candidates of smallest |posterior| [batch, n], in order."""
+        dev = posterior.device.index if device is None else device
+        check(lib().qldpc_select_positions_device(
+            self._g, None if plan is None else plan.handle, dev, int(posterior.shape[0]), _dp(posterior),
+            int(frames.shape[0]) if n_list is None else int(n_list), _dp(frames), int(first), int(count), _dp(pos),
+            int(pos.shape[1]), _stream_ptr(stream, dev)), "qldpc_select_positions_device")
+
+    def disclose_positions_device(self, ext, frames, pos, first: int, count: int, vals_out,
+                                  plan: "RatePlan | None" = None, n_list: int | None = None, stream=None,
+                                  device: int | None = None) -> None:
+        """Alice: vals_out [n_list, count] = ext[f, pos[f, first:first + count]] & 1
+        for the listed frames (ext: uint8 rows of ext.shape[1] >= n bytes)."""
+        dev = ext.device.index if device is None else device
+        check(lib().qldpc_disclose_positions_device(
+            self._g, None if plan is None else plan.handle, dev, int(frames.shape[0]) if n_list is None else int(n_list),
+            _dp(frames), _dp(ext), int(ext.shape[1]), _dp(pos), int(pos.shape[1]), int(first), int(count),
+            _dp(vals_out), _stream_ptr(stream, dev)), "qldpc_disclose_positions_device")
+
+    def reconcile_positions_round_device(self, params: Params, key, log_p, syndrome, frames, n_disc: int, pos, vals,
+                                         bits, iters, ok, plan: "RatePlan | None" = None, posterior=None,
+                                         n_list: int | None = None, stream=None, device: int | None = None) -> None:
+        """Bob: the listed frames of key [batch, n] decoded again with the
+        positions pos[f, :n_disc] pinned at vals [n_list, n_disc]; rows `frames`
+        of bits / iters / ok / posterior receive the results."""
+        dev = key.device.index if device is None else device
+        p = params.c()
+        check(lib().qldpc_reconcile_positions_round_device(
+            self._g, None if plan is None else plan.handle, dev, ctypes.byref(p), int(key.shape[0]), _dp(key),
+            _dp(log_p), _dp(syndrome), int(frames.shape[0]) if n_list is None else int(n_list), _dp(frames),
+            int(n_disc), _dp(pos), 0 if pos is None else int(pos.shape[1]), _dp(vals), _dp(bits), _dp(iters), _dp(ok),
+            _dp(posterior), _stream_ptr(stream, dev)), "qldpc_reconcile_positions_round_device")
+
     # ---- device-pointer entries (torch tensors as plumbing) ----
     def decode_device(self, params: Params, llr, syndrome, bits, iters, ok, posterior=None, stream=None,
                       device: int | None = None) -> None:
