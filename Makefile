@@ -56,6 +56,10 @@ $(CSRC)/blind.o: $(CSRC)/blind.hip $(CSRC)/decoder.hpp $(CSRC)/decoder_common.hp
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/decoder.hpp $(CSRC)/decoder_common.hpp $(CSRC)/exact_math.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# Error estimation at the reconciliation stage: syndrome weights, the QBER solve, corrected-error counts.
+$(CSRC)/estimate.o: $(CSRC)/estimate.hip $(CSRC)/decoder.hpp $(CSRC)/decoder_common.hpp $(CSRC)/exact_math.h $(CSRC)/estimate_math.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 # Key verification and privacy amplification: the batched Toeplitz hash.
 $(CSRC)/privacy.o: $(CSRC)/privacy.hip $(CSRC)/decoder.hpp $(CSRC)/decoder_common.hpp $(CSRC)/exact_math.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -71,7 +75,7 @@ $(CSRC)/privacy_block.o: $(CSRC)/privacy_block.hip $(CSRC)/decoder.hpp $(CSRC)/d
 # (run_trials.hip).  host_algos.cpp, loaders.cpp and relabel.cpp see no HIP header.
 HOST_HIP := capi plan layout run_trials
 HOST_OBJS := $(HOST_HIP:=.o) host_algos.o loaders.o relabel.o
-GRAPH_HPP := $(CSRC)/graph.hpp $(CSRC)/decoder.hpp include/qkd_ldpc_hip.h
+GRAPH_HPP := $(CSRC)/graph.hpp $(CSRC)/decoder.hpp include/qkd_ldpc_hip.h $(CSRC)/exact_math.h $(CSRC)/estimate_math.h
 
 $(CSRC)/capi.o: $(CSRC)/capi.hip $(GRAPH_HPP) $(CSRC)/loaders.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -94,7 +98,7 @@ $(CSRC)/loaders.o: $(CSRC)/loaders.cpp $(CSRC)/loaders.hpp
 $(CSRC)/relabel.o: $(CSRC)/relabel.cpp $(CSRC)/relabel.hpp
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 
-$(LIB): $(CSRC)/decoder.o $(CSRC)/decoder_v2.o $(CSRC)/decoder_fpl.o $(CSRC)/trials.o $(CSRC)/order.o $(CSRC)/parties.o $(CSRC)/blind.o $(CSRC)/select.o $(CSRC)/privacy.o $(CSRC)/privacy_block.o $(addprefix $(CSRC)/,$(HOST_OBJS))
+$(LIB): $(CSRC)/decoder.o $(CSRC)/decoder_v2.o $(CSRC)/decoder_fpl.o $(CSRC)/trials.o $(CSRC)/order.o $(CSRC)/parties.o $(CSRC)/blind.o $(CSRC)/select.o $(CSRC)/estimate.o $(CSRC)/privacy.o $(CSRC)/privacy_block.o $(addprefix $(CSRC)/,$(HOST_OBJS))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -lz -o $@
 
 # Diagnostic build with per-phase s_memtime stamps (never the product).  On the
@@ -107,7 +111,7 @@ $(CSRC)/decoder_v2_st.o: $(CSRC)/decoder_v2.hip $(CSRC)/decoder_common.hpp $(CSR
 	$(HIPCC) $(HIPFLAGS) $(V2FLAGS) -DQL_PHASE_STAMPS -c $< -o $@
 $(CSRC)/capi_st.o: $(CSRC)/capi.hip $(GRAPH_HPP) $(CSRC)/loaders.hpp
 	$(HIPCC) $(HIPFLAGS) -DQL_PHASE_STAMPS -c $< -o $@
-$(STAMPLIB): $(CSRC)/decoder_st.o $(CSRC)/decoder_v2_st.o $(CSRC)/decoder_fpl.o $(CSRC)/trials.o $(CSRC)/order.o $(CSRC)/parties.o $(CSRC)/blind.o $(CSRC)/select.o $(CSRC)/privacy.o $(CSRC)/privacy_block.o $(addprefix $(CSRC)/,$(patsubst capi.o,capi_st.o,$(HOST_OBJS)))
+$(STAMPLIB): $(CSRC)/decoder_st.o $(CSRC)/decoder_v2_st.o $(CSRC)/decoder_fpl.o $(CSRC)/trials.o $(CSRC)/order.o $(CSRC)/parties.o $(CSRC)/blind.o $(CSRC)/select.o $(CSRC)/estimate.o $(CSRC)/privacy.o $(CSRC)/privacy_block.o $(addprefix $(CSRC)/,$(patsubst capi.o,capi_st.o,$(HOST_OBJS)))
 	mkdir -p $(PKG)/diag
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -lz -o $@
 
@@ -157,7 +161,7 @@ LLVM_BIN := /opt/rocm/lib/llvm/bin
 SANFLAGS := -fsanitize=address -fsanitize=undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g
 HIP_SAN := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined \
            -Xarch_host -fno-omit-frame-pointer -g
-ASAN_DEV_OBJS := $(ASAN)/decoder.o $(ASAN)/decoder_v2.o $(ASAN)/decoder_fpl.o $(ASAN)/trials.o $(ASAN)/order.o $(ASAN)/parties.o $(ASAN)/blind.o $(ASAN)/select.o $(ASAN)/privacy.o $(ASAN)/privacy_block.o
+ASAN_DEV_OBJS := $(ASAN)/decoder.o $(ASAN)/decoder_v2.o $(ASAN)/decoder_fpl.o $(ASAN)/trials.o $(ASAN)/order.o $(ASAN)/parties.o $(ASAN)/blind.o $(ASAN)/select.o $(ASAN)/estimate.o $(ASAN)/privacy.o $(ASAN)/privacy_block.o
 $(ASAN)/%.o: $(CSRC)/%.hip $(GRAPH_HPP) $(CSRC)/decoder_common.hpp $(CSRC)/exact_math.h $(CSRC)/relabel.hpp $(CSRC)/loaders.hpp
 	mkdir -p $(ASAN)
 	$(HIPCC) $(HIPFLAGS) $(HIP_SAN) -c $< -o $@
@@ -203,5 +207,5 @@ ab:
 	for f in $(HOST_HIP); do \
 	    if [ -n "$(AB_CAPI)" ]; then $(HIPCC) $(HIPFLAGS) $(AB_FLAGS) -c $(CSRC)/$$f.hip -o $(AB_DIR)/$$f.o || exit 1; \
 	    else cp $(CSRC)/$$f.o $(AB_DIR)/$$f.o || exit 1; fi; done
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(AB_DIR)/decoder_v2.o $(CSRC)/decoder.o $(CSRC)/decoder_fpl.o $(CSRC)/trials.o $(CSRC)/order.o $(CSRC)/parties.o $(CSRC)/blind.o $(CSRC)/select.o $(CSRC)/privacy.o $(CSRC)/privacy_block.o $(addprefix $(AB_DIR)/,$(HOST_HIP:=.o)) $(addprefix $(CSRC)/,$(filter-out $(HOST_HIP:=.o),$(HOST_OBJS))) -lz -o $(AB_DIR)/libqkdldpc_hip.so
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(AB_DIR)/decoder_v2.o $(CSRC)/decoder.o $(CSRC)/decoder_fpl.o $(CSRC)/trials.o $(CSRC)/order.o $(CSRC)/parties.o $(CSRC)/blind.o $(CSRC)/select.o $(CSRC)/estimate.o $(CSRC)/privacy.o $(CSRC)/privacy_block.o $(addprefix $(AB_DIR)/,$(HOST_HIP:=.o)) $(addprefix $(CSRC)/,$(filter-out $(HOST_HIP:=.o),$(HOST_OBJS))) -lz -o $(AB_DIR)/libqkdldpc_hip.so
 .PHONY: ab

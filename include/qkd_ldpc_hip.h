@@ -491,6 +491,115 @@ int qldpc_reconcile_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullabl
                           uint8_t *bits_out, uint32_t *iters_out, uint8_t *synd_ok_out,
                           double *posterior_out /* nullable */);
 
+/* ---- Error estimation at the reconciliation stage ---------------------------------
+ * Where the QBER comes from (Kiktenko, Malyshev, Bozhedarov, Pozhar, Anufriev,
+ * Fedorov, arXiv:1810.05841): Bob estimates it from data the exchange already
+ * holds, before the decode (the log_p of qldpc_reconcile_batch[_device]) and
+ * after it (the q of the secret-length formulas).  Both are computed by Bob
+ * alone: the estimates need nothing new from the channel.
+ *
+ * Definitions.  Bob's extended key x~_f: with a plan his key bits at the
+ * plan's key positions and 0 at punctured and shortened positions; without a
+ * plan his key.  Difference syndrome: z_f = s_A,f XOR H x~_f.  A check row j is
+ * INFORMATIVE when it has no punctured neighbour (Alice's private fill makes
+ * such a row uniform) and its effective degree d_j = deg_j - #shortened
+ * neighbours is >= 1; without a plan every row of degree >= 1 is.  The CLASSES
+ * are the distinct effective degrees of the informative rows, ascending,
+ * d_1 < ... < d_C, with row counts N_c; R = sum of N_c.  The per-frame
+ * statistic K_f (int32) is the number of informative rows with z_f[j] = 1.
+ *
+ * Estimator: method of moments on the weight.  A row of effective degree d
+ * differs with probability (1 - (1 - 2q)^d) / 2, so q^ solves g(q^) = K on
+ * [q_min, q_max] with
+ *
+ *     g(q) = sum over c of  N_c * (1 - (1 - 2q)^d_c) / 2
+ *
+ * g rises with q: the root is unique.  Only IEEE-754 binary64 add, subtract,
+ * multiply and compare take part, in a fixed order (csrc/estimate_math.h, one
+ * function for the kernel and the host entry): t = 1 - 2q; the powers t^d by
+ * repeated multiplication from 1.0, carried from d_c to d_(c+1); the terms
+ * N_c * (0.5 * (1 - t^d_c)) added in ascending class order into an accumulator
+ * that starts at 0.0.  With F = frames_per_weight: if F g(q_min) >= K then
+ * q^ = q_min; if F g(q_max) <= K then q^ = q_max; otherwise bisect, lo = q_min,
+ * hi = q_max, mid = 0.5 (lo + hi), lo = mid when F g(mid) < K, else hi = mid,
+ * until mid equals an end or 64 steps are made; q^ = 0.5 (lo + hi).  The same
+ * weight gives the same bits on the host and on the device.
+ *
+ * Bounds: 0 < q_min <= q_max < 0.5, else QLDPC_EINVAL (NaN included): q^ lies
+ * in (0, 0.5) and log_p is finite and positive.
+ *
+ * log_p = log1p((1 - 2 q^) / q^) = log((1 - q^) / q^), with the library's
+ * restatement of glibc's log1p (qldpc_selftest_math_device fn 3): bit-identical
+ * to the C library's log1p of that argument.  It is NOT claimed to equal
+ * qldpc_log_p(q^) bit for bit: that function calls log().
+ *
+ * R == 0 (for example every row has a punctured neighbour): nothing can be
+ * estimated.  Every estimating entry returns QLDPC_EINVAL ("no informative
+ * rows") and launches nothing.
+ *
+ * Corrected errors: E_f = the key positions at which Bob's key differs from
+ * the decoded frame.  With a plan #{i : position i is a key position,
+ * key[src(i)] != bits[i]}, src(i) the position's index among the key
+ * positions: punctured and shortened positions do not count.  Without a plan
+ * the Hamming distance of the two n-bit rows.  It is the frame's exact error
+ * count when the frame decoded to Alice's key, i.e. for frames that verified.
+ * Only bit 0 of every key, syndrome and frame byte is read.
+ *
+ * qldpc_estimate_classes (host only; works on a qldpc_graph_create_host
+ * graph): *n_classes = C, and the first min(C, cap) classes to degree_out /
+ * rows_out (NULL allowed when cap == 0).  C == 0 is R == 0.
+ *
+ * qldpc_qber_from_weight (host only): qber_out[i] (and log_p_out[i]) from
+ * weight[i], i < count.  frames_per_weight = 1: per-frame weights; F: each
+ * weight is a sum over F frames (a pooled estimate).  A weight outside
+ * [0, F R] is refused.
+ *
+ * qldpc_estimate_qber_device: K_f to d_weight_out, q^_f to d_qber_out, log_p_f
+ * to d_log_p_out, [batch] each, each nullable (not all three).  The key layout
+ * and strides are those of qldpc_reconcile_batch_device: with a plan d_key is
+ * [batch][n] and the first n_key entries of a row are read.  When only
+ * d_weight_out is given nothing is solved and the bounds are not looked at.
+ * d_log_p_out can be handed to qldpc_reconcile_batch_device on the same stream
+ * with no synchronisation in between.  Two launches: one workgroup per frame
+ * for the weights, one thread per frame for the solve.  Works on every graph
+ * layout; n is bounded by the LDS fit of the key in bit words (as for
+ * qldpc_syndrome_batch_device); the solve takes at most 64 classes
+ * (QLDPC_EUNSUP beyond; qldpc_qber_from_weight takes any number).
+ *
+ * qldpc_corrected_errors_device: E_f to d_errors_out [batch]; d_bits is
+ * [batch][n], a decoded frame.
+ *
+ * qldpc_estimate_qber_batch / qldpc_corrected_errors_batch: the same on HOST
+ * buffers, synchronous, sharded over the graph's devices like
+ * qldpc_reconcile_batch.
+ *
+ * A plan is tied to the adjacency of the graph it was created for (its row
+ * table is built then): with a graph of another adjacency the estimating
+ * entries return QLDPC_EINVAL.
+ *
+ * Arguments are checked in the two-party order: NULL graph, batch < 0,
+ * batch == 0 (OK), NULL buffers, then the bounds (when something is solved),
+ * the plan's graph and R == 0, then the plan on the device, the device, the
+ * LDS fit.  Through batch == 0 no device is touched. */
+int qldpc_estimate_classes(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t cap,
+                           int32_t *n_classes, int32_t *degree_out, int32_t *rows_out);
+int qldpc_qber_from_weight(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t count,
+                           const int64_t *weight, int64_t frames_per_weight, double q_min, double q_max,
+                           double *qber_out, double *log_p_out /* nullable */);
+int qldpc_estimate_qber_device(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t device,
+                               int32_t batch, const uint8_t *d_key, const uint8_t *d_syndrome, double q_min,
+                               double q_max, int32_t *d_weight_out /* nullable */, double *d_qber_out /* nullable */,
+                               double *d_log_p_out /* nullable */, void *stream);
+int qldpc_estimate_qber_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t batch,
+                              const uint8_t *key, const uint8_t *syndrome, double q_min, double q_max,
+                              int32_t *weight_out /* nullable */, double *qber_out /* nullable */,
+                              double *log_p_out /* nullable */);
+int qldpc_corrected_errors_device(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t device,
+                                  int32_t batch, const uint8_t *d_key, const uint8_t *d_bits, int32_t *d_errors_out,
+                                  void *stream);
+int qldpc_corrected_errors_batch(qldpc_graph *g, const qldpc_rate_plan *plan /* nullable */, int32_t batch,
+                                 const uint8_t *key, const uint8_t *bits, int32_t *errors_out);
+
 /* ---- Blind reconciliation: disclosure rounds for frames that failed -------------
  * A frame whose decode ended with syndromes_match == 0 need not be lost, nor
  * the batch be sent again under another rate plan: in blind reconciliation

@@ -22,6 +22,12 @@ privacy.amplify shortens the verified frames by what the exchange leaked
 (privacy.leaked_bits, privacy.secret_length).  toeplitz_hash_block[_device]
 hashes the concatenation of a list of frames' keys as one block, up to 2^27
 bits (privacy.block_tag, privacy.block_secret_length, privacy.block_amplify).
+
+The QBER those steps take comes from the exchange itself (estimate.py):
+estimate.prior gives Bob's log_p before the decode from the syndrome weight
+(Graph.estimate_qber[_device], Graph.estimate_classes, Graph.qber_from_weight),
+estimate.corrected_errors and estimate.block_qber the measured QBER of the
+verified frames after it (Graph.corrected_errors[_device]).
 """
 from ._lib import (ALGORITHM_NAMES, ANMSA, AOMSA, NMSA, OMSA, SPA, SPA_LIN, SELECT_MAX, TRACE_NONE, Params, QLDPCError,
                    exported_symbols, lib, log_p, version)
@@ -31,7 +37,7 @@ from .graph import (DecodeOutput, Graph, HMatrix, RatePlan, TraceOutput, TrialsO
                     trial_seeds, trials_device, trials_rate_adapt_device, xoshiro_state)
 from .trials import bsc_frames
 from .codes import regular_code
-from . import blind, privacy
+from . import blind, estimate, privacy
 from .blind import BlindOutput, SymmetricOutput, blind_efficiency, blind_reconcile, symmetric_reconcile
 
 __all__ = [
@@ -41,5 +47,5 @@ __all__ = [
     "trial_seeds", "trials_device", "RatePlan", "adapt_code_rate", "trials_rate_adapt_device", "xoshiro_state",
     "load_matrix", "bsc_frames", "TraceOutput", "TRACE_NONE", "blind", "BlindOutput", "blind_efficiency",
     "blind_reconcile", "SymmetricOutput", "symmetric_reconcile", "SELECT_MAX", "privacy", "toeplitz_hash", "toeplitz_hash_device",
-    "toeplitz_block_workspace", "toeplitz_hash_block", "toeplitz_hash_block_device",
+    "toeplitz_block_workspace", "toeplitz_hash_block", "toeplitz_hash_block_device", "estimate",
 ]

@@ -121,6 +121,13 @@ _SIGNATURES = {
     "qldpc_extract_key_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _P]),
     "qldpc_syndrome_batch": (_I32, [_P, _P, _I32, _P, _P, _P, _P]),
     "qldpc_reconcile_batch": (_I32, [_P, _P, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "qldpc_estimate_classes": (_I32, [_P, _P, _I32, _PI32, _P, _P]),
+    "qldpc_qber_from_weight": (_I32, [_P, _P, _I32, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "qldpc_estimate_qber_device": (_I32, [_P, _P, _I32, _I32, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P,
+                                          _P]),
+    "qldpc_estimate_qber_batch": (_I32, [_P, _P, _I32, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P]),
+    "qldpc_corrected_errors_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "qldpc_corrected_errors_batch": (_I32, [_P, _P, _I32, _P, _P, _P]),
     "qldpc_failed_frames_device": (_I32, [_I32, _P, _P, _P, _P]),
     "qldpc_disclose_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _P, _P, _P]),
     "qldpc_reconcile_round_device": (_I32, [_P, _P, _I32, ctypes.POINTER(qldpc_params), _I32, _P, _P, _P, _I32, _P,

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "estimate_math.h"
 #include "graph.hpp"
 #include "loaders.hpp"
 
@@ -56,6 +57,46 @@ int upload_tables(DeviceGraph &dg, const qldpc_graph &g, const GraphTables &t) {
     return QLDPC_OK;
 }
 
+// Error estimation: the row table of the graph under a plan's position classes
+// (cls == NULL: no plan) and the degree classes of its informative rows.
+void est_row_table(const qldpc_graph &g, const uint8_t *cls, EstTable &e) {
+    e.row_d.assign(std::max(g.m, 1), 0);
+    std::map<int32_t, int32_t> classes;
+    for (int j = 0; j < g.m; ++j) {
+        int d = g.h_row_deg[j];
+        for (int k = 0; cls && k < g.h_row_deg[j]; ++k) {
+            const uint8_t c = cls[g.h_ell_col[(size_t)k * g.m + j]];
+            if (c == 1) {  // a punctured neighbour: Alice's private fill makes the row uniform
+                d = 0;
+                break;
+            }
+            d -= c == 2;
+        }
+        e.row_d[j] = d;
+        if (d > 0) ++classes[d];
+    }
+    e.degree.clear();
+    e.rows.clear();
+    e.informative = 0;
+    for (auto &c : classes) {
+        e.degree.push_back(c.first);
+        e.rows.push_back(c.second);
+        e.informative += c.second;
+    }
+}
+
+uint64_t adjacency_hash(const qldpc_graph &g) {  // FNV-1a over n, m, the row degrees and the row-ELL columns
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto mix = [&h](uint32_t v) {
+        for (int b = 0; b < 4; ++b) h = (h ^ ((v >> (8 * b)) & 0xffu)) * 0x100000001b3ull;
+    };
+    mix((uint32_t)g.n);
+    mix((uint32_t)g.m);
+    for (int32_t v : g.h_row_deg) mix((uint32_t)v);
+    for (int32_t v : g.h_ell_col) mix((uint32_t)v);
+    return h;
+}
+
 // host_only: plan and relabel without any device (introspection; the graph
 // has no devices and cannot decode).
 // bit_nodes (col_ptr / row_idx, the reference's H_matrix::bit_nodes in its
@@ -69,6 +110,11 @@ int build_graph(int32_t n, int32_t m, const int32_t *row_ptr, const int32_t *col
     std::unique_ptr<qldpc_graph> g;
     GraphTables t;
     if (int rc = build_layout(n, m, row_ptr, col_idx, col_ptr, row_idx, g, t, layout)) return rc;
+    g->h_ell_col = t.ell_col;
+    g->h_row_deg = t.row_deg;
+    g->adjacency = adjacency_hash(*g);
+    est_row_table(*g, nullptr, g->est);
+    g->est.row_d.clear();  // (it is row_deg: the launches pass that)
     if (host_only) {
         *out = g.release();
         return QLDPC_OK;
@@ -1326,6 +1372,9 @@ int qldpc_rate_plan_create(qldpc_graph *g, int32_t n_punct, const int32_t *punct
     auto plan = std::make_unique<qldpc_rate_plan>();
     plan->n_punct = n_punct;
     plan->n_short = n_short;
+    est_row_table(*g, cls.data(), plan->est);  // once per (graph, plan): the error estimate's row table
+    plan->adjacency = g->adjacency;
+    plan->cls = cls;
     DeviceScope restore;  // (a host-only graph: the plan lives on no device, and none is touched)
     if (int rc = g->devs.empty() ? QLDPC_OK : restore.save()) return rc;
     for (auto &dg : g->devs) {
@@ -1333,7 +1382,7 @@ int qldpc_rate_plan_create(qldpc_graph *g, int32_t n_punct, const int32_t *punct
         qldpc_rate_plan::Dev d;
         d.device = dg->device;
         int rc;
-        if ((rc = d.cls.upload(cls)) || (rc = d.src.upload(src))) return rc;
+        if ((rc = d.cls.upload(cls)) || (rc = d.src.upload(src)) || (rc = d.row_d.upload(plan->est.row_d))) return rc;
         plan->devs.push_back(std::move(d));
     }
     *out = plan.release();
@@ -1598,6 +1647,234 @@ int qldpc_reconcile_batch(qldpc_graph *g, const qldpc_rate_plan *plan, const qld
             if (r) return r;
             if (e != hipSuccess) return hip_fail(e, "reconcile_batch");
             return split_check(g, dg, io.stream);
+        });
+}
+
+// ---- error estimation at the reconciliation stage ----------------------------------
+// Argument checks, in the two-party order: NULL graph, batch < 0, batch == 0
+// (OK), NULL buffers, the q bounds (when something is solved), the plan's
+// graph and R == 0, the plan on the device, the device, the LDS fit.
+namespace {
+
+const EstTable *est_table(const qldpc_graph *g, const qldpc_rate_plan *plan) { return plan ? &plan->est : &g->est; }
+
+int est_plan_check(const qldpc_graph *g, const qldpc_rate_plan *plan) {
+    if (plan && plan->adjacency != g->adjacency)
+        return fail(QLDPC_EINVAL, "the rate plan was created for a graph of another adjacency: its row table does not apply");
+    return QLDPC_OK;
+}
+
+int est_bounds_check(double q_min, double q_max) {
+    if (!(q_min > 0.0) || !(q_max < 0.5) || !(q_min <= q_max))  // (NaN fails each)
+        return fail(QLDPC_EINVAL, "the estimate's bounds must satisfy 0 < q_min <= q_max < 0.5");
+    return QLDPC_OK;
+}
+
+int est_rows_check(const EstTable *e) {
+    if (e->informative == 0)
+        return fail(QLDPC_EINVAL, "no informative rows: every check row has a punctured neighbour or only shortened ones");
+    return QLDPC_OK;
+}
+
+int est_fits(const qldpc_graph *g, bool with_plan) {
+    const size_t lds = syndrome_weight_lds(g->n, with_plan);
+    if (lds <= LDS_MAX_BYTES) return QLDPC_OK;
+    return fail(QLDPC_EUNSUP, "n = " + std::to_string(g->n) + ": the syndrome-weight kernel keeps the key in LDS (" +
+                                  std::to_string(lds) + " bytes > " + std::to_string(LDS_MAX_BYTES) + ")");
+}
+
+int est_classes_fit(const EstTable *e) {
+    if (e->degree.size() <= (size_t)EST_MAX_CLASSES) return QLDPC_OK;
+    return fail(QLDPC_EUNSUP, std::to_string(e->degree.size()) + " degree classes: the solve kernel takes at most " +
+                                  std::to_string(EST_MAX_CLASSES) + " (qldpc_qber_from_weight solves any number)");
+}
+
+// The weights, then (qber or log_p wanted) the solve, on `s`; the current
+// device is dg's.  d_weight NULL: the weights go to the stream's workspace.
+int estimate_window(qldpc_graph *g, DeviceGraph *dg, const qldpc_rate_plan::Dev *pd, const EstTable *e, int batch,
+                    const uint8_t *d_key, const uint8_t *d_synd, double q_min, double q_max, int32_t *d_weight,
+                    double *d_qber, double *d_log_p, hipStream_t s) {
+    if (!d_weight) {
+        std::lock_guard<std::mutex> lk(dg->mu);
+        Workspace *w = workspace(dg, s);
+        if (int r = grow(w->est_frames, (size_t)batch, s, [&] { return w->est_weight.alloc((size_t)batch); })) return r;
+        d_weight = w->est_weight.get();
+    }
+    HIP_TRY(launch_syndrome_weight(g->n, g->m, dg->ell_col.get(), dg->row_deg.get(),
+                                   pd ? pd->row_d.get() : dg->row_deg.get(), pd ? pd->cls.get() : nullptr,
+                                   pd ? pd->src.get() : nullptr, batch, d_key, d_synd, d_weight, s));
+    if (d_qber || d_log_p)
+        HIP_TRY(launch_estimate_solve(batch, (int)e->degree.size(), e->degree.data(), e->rows.data(), d_weight, q_min,
+                                      q_max, d_qber, d_log_p, s));
+    return QLDPC_OK;
+}
+
+}  // namespace
+
+int qldpc_estimate_classes(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t cap, int32_t *n_classes,
+                           int32_t *degree_out, int32_t *rows_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (cap < 0 || !n_classes || (cap > 0 && (!degree_out || !rows_out)))
+        return fail(QLDPC_EINVAL, "cap must be >= 0 and the outputs not NULL");
+    if (int r = est_plan_check(g, plan)) return r;
+    const EstTable *e = est_table(g, plan);
+    *n_classes = (int32_t)e->degree.size();
+    for (size_t c = 0; c < e->degree.size() && c < (size_t)cap; ++c) {
+        degree_out[c] = e->degree[c];
+        rows_out[c] = e->rows[c];
+    }
+    return QLDPC_OK;
+}
+
+int qldpc_qber_from_weight(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t count, const int64_t *weight,
+                           int64_t frames_per_weight, double q_min, double q_max, double *qber_out,
+                           double *log_p_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (count < 0) return fail(QLDPC_EINVAL, "count must be >= 0");
+    if (count == 0) return QLDPC_OK;
+    if (!weight || !qber_out) return fail(QLDPC_EINVAL, "NULL host buffer");
+    if (frames_per_weight < 1) return fail(QLDPC_EINVAL, "frames_per_weight must be >= 1");
+    int rc;
+    if ((rc = est_bounds_check(q_min, q_max)) || (rc = est_plan_check(g, plan))) return rc;
+    const EstTable *e = est_table(g, plan);
+    if ((rc = est_rows_check(e))) return rc;
+    if (frames_per_weight > (INT64_MAX >> 1) / e->informative)
+        return fail(QLDPC_EINVAL, "frames_per_weight is too large");
+    const int64_t most = frames_per_weight * e->informative;
+    for (int32_t i = 0; i < count; ++i)
+        if (weight[i] < 0 || weight[i] > most)
+            return fail(QLDPC_EINVAL, "a weight lies outside [0, frames_per_weight * informative rows]");
+    const ql_exact::EstClasses cl = {(int32_t)e->degree.size(), e->degree.data(), e->rows.data()};
+    for (int32_t i = 0; i < count; ++i) {
+        qber_out[i] = ql_exact::est_qber(cl, weight[i], frames_per_weight, q_min, q_max);
+        if (log_p_out) log_p_out[i] = ql_exact::est_log_p(qber_out[i]);
+    }
+    return QLDPC_OK;
+}
+
+int qldpc_estimate_qber_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t batch,
+                               const uint8_t *d_key, const uint8_t *d_syndrome, double q_min, double q_max,
+                               int32_t *d_weight_out, double *d_qber_out, double *d_log_p_out, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!d_key || !d_syndrome || (!d_weight_out && !d_qber_out && !d_log_p_out))
+        return fail(QLDPC_EINVAL, "NULL device buffer");
+    const bool solve = d_qber_out || d_log_p_out;
+    int rc;
+    if (solve && (rc = est_bounds_check(q_min, q_max))) return rc;
+    if ((rc = est_plan_check(g, plan))) return rc;
+    const EstTable *e = est_table(g, plan);
+    if ((rc = est_rows_check(e))) return rc;
+    const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, device) : nullptr;
+    if (plan && !pd) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    DeviceGraph *dg = find_dev(g, device);
+    if (!dg) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    if ((rc = est_fits(g, plan != nullptr)) || (solve && (rc = est_classes_fit(e)))) return rc;
+    DeviceScope ds;
+    if ((rc = ds.enter(device))) return rc;
+    return estimate_window(g, dg, pd, e, batch, d_key, d_syndrome, q_min, q_max, d_weight_out, d_qber_out, d_log_p_out,
+                           (hipStream_t)stream);
+}
+
+int qldpc_corrected_errors_device(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t device, int32_t batch,
+                                  const uint8_t *d_key, const uint8_t *d_bits, int32_t *d_errors_out, void *stream) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!d_key || !d_bits || !d_errors_out) return fail(QLDPC_EINVAL, "NULL device buffer");
+    const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, device) : nullptr;
+    if (plan && !pd) return fail(QLDPC_EINVAL, "rate plan does not live on that device");
+    if (!find_dev(g, device)) return fail(QLDPC_EINVAL, "graph does not live on that device");
+    DeviceScope ds;
+    if (int r = ds.enter(device)) return r;
+    HIP_TRY(launch_corrected_errors(g->n, pd ? pd->cls.get() : nullptr, pd ? pd->src.get() : nullptr, batch, d_key,
+                                    d_bits, d_errors_out, (hipStream_t)stream));
+    return QLDPC_OK;
+}
+
+int qldpc_estimate_qber_batch(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t batch, const uint8_t *key,
+                              const uint8_t *syndrome, double q_min, double q_max, int32_t *weight_out,
+                              double *qber_out, double *log_p_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!key || !syndrome || (!weight_out && !qber_out && !log_p_out)) return fail(QLDPC_EINVAL, "NULL host buffer");
+    const bool solve = qber_out || log_p_out;
+    int rc;
+    if (solve && (rc = est_bounds_check(q_min, q_max))) return rc;
+    if ((rc = est_plan_check(g, plan))) return rc;
+    const EstTable *e = est_table(g, plan);
+    if ((rc = est_rows_check(e)) || (rc = plan_on_every_device(g, plan))) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot estimate on a device");
+    if ((rc = est_fits(g, plan != nullptr)) || (solve && (rc = est_classes_fit(e)))) return rc;
+    const size_t n = (size_t)g->n, m = (size_t)g->m;
+    return for_each_shard(
+        g, batch, "a host-only graph cannot estimate on a device",
+        [&](DeviceGraph *dg, HostIO &io, int f0, int nb) -> int {
+            if (int r = io.reserve((size_t)nb, n, m, false, false, true)) return r;
+            const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, dg->device) : nullptr;
+            DevBuf<int32_t> d_w;  // for this call alone (allocated before anything is enqueued)
+            DevBuf<double> d_q;
+            if (int r = d_w.alloc((size_t)nb)) return r;
+            if (int r = qber_out ? d_q.alloc((size_t)nb) : QLDPC_OK) return r;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(io.key.get(), key + f0 * n, nb * n, hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(hipMemcpyAsync(io.synd.get(), syndrome + f0 * m, nb * m, hipMemcpyHostToDevice, io.stream));
+                if (int r = estimate_window(g, dg, pd, e, nb, io.key.get(), io.synd.get(), q_min, q_max, d_w.get(),
+                                            d_q.get(), log_p_out ? io.logp.get() : nullptr, io.stream))
+                    return r;
+                if (weight_out)
+                    HIP_TRY(hipMemcpyAsync(weight_out + f0, d_w.get(), nb * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                           io.stream));
+                if (qber_out)
+                    HIP_TRY(hipMemcpyAsync(qber_out + f0, d_q.get(), nb * sizeof(double), hipMemcpyDeviceToHost,
+                                           io.stream));
+                if (log_p_out)
+                    HIP_TRY(hipMemcpyAsync(log_p_out + f0, io.logp.get(), nb * sizeof(double), hipMemcpyDeviceToHost,
+                                           io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t err = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (err != hipSuccess) return hip_fail(err, "estimate_qber_batch");
+            return QLDPC_OK;
+        });
+}
+
+int qldpc_corrected_errors_batch(qldpc_graph *g, const qldpc_rate_plan *plan, int32_t batch, const uint8_t *key,
+                                 const uint8_t *bits, int32_t *errors_out) {
+    if (!g) return fail(QLDPC_EINVAL, "graph is NULL");
+    if (batch < 0) return fail(QLDPC_EINVAL, "batch must be >= 0");
+    if (batch == 0) return QLDPC_OK;
+    if (!key || !bits || !errors_out) return fail(QLDPC_EINVAL, "NULL host buffer");
+    if (int rc = plan_on_every_device(g, plan)) return rc;
+    if (g->devs.empty()) return fail(QLDPC_EINVAL, "a host-only graph cannot count errors on a device");
+    const size_t n = (size_t)g->n, m = (size_t)g->m;
+    return for_each_shard(
+        g, batch, "a host-only graph cannot count errors on a device",
+        [&](DeviceGraph *dg, HostIO &io, int f0, int nb) -> int {
+            if (int r = io.reserve((size_t)nb, n, m, false, false, true)) return r;
+            const qldpc_rate_plan::Dev *pd = plan ? plan_dev(plan, dg->device) : nullptr;
+            DevBuf<uint8_t> d_bits;  // for this call alone (allocated before anything is enqueued)
+            DevBuf<int32_t> d_err;
+            if (int r = d_bits.alloc((size_t)nb * n)) return r;
+            if (int r = d_err.alloc((size_t)nb)) return r;
+            auto enqueue = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(io.key.get(), key + f0 * n, nb * n, hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(hipMemcpyAsync(d_bits.get(), bits + f0 * n, nb * n, hipMemcpyHostToDevice, io.stream));
+                HIP_TRY(launch_corrected_errors(g->n, pd ? pd->cls.get() : nullptr, pd ? pd->src.get() : nullptr, nb,
+                                                io.key.get(), d_bits.get(), d_err.get(), io.stream));
+                HIP_TRY(hipMemcpyAsync(errors_out + f0, d_err.get(), nb * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                       io.stream));
+                return QLDPC_OK;
+            };
+            const int r = enqueue();
+            const hipError_t err = hipStreamSynchronize(io.stream);  // nothing of this call stays in flight
+            if (r) return r;
+            if (err != hipSuccess) return hip_fail(err, "corrected_errors_batch");
+            return QLDPC_OK;
         });
 }
 

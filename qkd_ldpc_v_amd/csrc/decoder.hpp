@@ -357,6 +357,28 @@ hipError_t launch_round_frames(int n, int m, int batch, int n_punct, const uint8
                                int n_list, const int32_t *list, const uint8_t *key, const double *log_p,
                                const uint8_t *synd, int n_disc, const int32_t *disc, const uint8_t *vals,
                                double *llr, uint8_t *synd_ws, hipStream_t stream);
+// ---- error estimation at the reconciliation stage (estimate.hip) ----------------
+// weight[f] = the informative rows j (row_d[j] > 0: the row's effective degree,
+// 0 = not informative) at which synd[f][j] differs from H * Bob's extended key
+// (key bits at the plan's key positions, 0 elsewhere; cls / src nullable: no
+// plan).  Dynamic LDS: the key, and with a plan the extended key, as bit words.
+constexpr int EST_MAX_CLASSES = 64;  // degree classes the solve kernel takes as a kernel argument
+inline size_t syndrome_weight_lds(int n, bool with_plan) {
+    return ((size_t)((n + 31) / 32) + (with_plan ? 2 * (size_t)((n + 63) / 64) : 0)) * sizeof(uint32_t);
+}
+hipError_t launch_syndrome_weight(int n, int m, const int32_t *ell_col, const int32_t *row_deg, const int32_t *row_d,
+                                  const uint8_t *cls, const int32_t *src, int batch, const uint8_t *key,
+                                  const uint8_t *synd, int32_t *weight, hipStream_t stream);
+// qber[f], log_p[f] (each nullable) from weight[f] and the class table (host
+// arrays of n_classes <= EST_MAX_CLASSES entries): estimate_math.h, one thread per frame.
+hipError_t launch_estimate_solve(int batch, int n_classes, const int32_t *degree, const int32_t *rows,
+                                 const int32_t *weight, double q_min, double q_max, double *qber, double *log_p,
+                                 hipStream_t stream);
+// errors[f] = the key positions at which key[f] differs from bits[f]: with a
+// plan #{i : cls[i] == 0, key[f][src[i]] != bits[f][i]}, without one the
+// Hamming distance of the two n-byte rows.
+hipError_t launch_corrected_errors(int n, const uint8_t *cls, const int32_t *src, int batch, const uint8_t *key,
+                                   const uint8_t *bits, int32_t *errors, hipStream_t stream);
 // ---- symmetric blind rounds: per-frame positions (select.hip, blind.hip) --------
 // pos[f][first .. first + count) = the `count` candidate positions of frame
 // f = list[j] (NULL: f = j) with the smallest (|posterior| as 63 bits, index), in

@@ -163,6 +163,9 @@ struct Workspace {  // per (device, stream): frame counter + decoder scratch
     // ... and of a traced decode: 64 per-lane counters per tile (FplTrace::cnt), capacity in tiles
     DevBuf<uint32_t> fpl_trace_cnt;
     size_t fpl_trace_tiles = 0;
+    // the syndrome weights of an estimate whose caller takes only q / log_p, capacity in frames
+    DevBuf<int32_t> est_weight;
+    size_t est_frames = 0;
     // kernel timing (qldpc_set_kernel_timing): events around the last decode launch
     Event ev0, ev1;
     bool ev_recorded = false;
@@ -308,15 +311,32 @@ struct GraphTables {
 
 }  // namespace qldpc
 
+namespace qldpc {
+// Error estimation (capi.hip est_row_table): per check row its effective degree
+// when it is informative — no punctured neighbour, at least one neighbour that
+// is not shortened — else 0, and the classes of the informative rows: the
+// distinct effective degrees, ascending, with their row counts.
+struct EstTable {
+    std::vector<int32_t> row_d, degree, rows;
+    int64_t informative = 0;  // R, the sum of rows[]
+};
+}  // namespace qldpc
+
 // Rate-adaptation plan: per position its class (0 key, 1 punctured, 2
-// shortened) and source index, replicated on the graph's devices.
+// shortened) and source index, replicated on the graph's devices; the class
+// bytes on the host too, and the estimator's row table of the graph the plan
+// was created for (adjacency: that graph's qldpc_graph::adjacency).
 struct qldpc_rate_plan {
     struct Dev {
         int device;
         qldpc::DevBuf<uint8_t> cls;
         qldpc::DevBuf<int32_t> src;
+        qldpc::DevBuf<int32_t> row_d;
     };
     int n_punct = 0, n_short = 0;
+    std::vector<uint8_t> cls;
+    qldpc::EstTable est;
+    uint64_t adjacency = 0;
     std::vector<Dev> devs;
 };
 
@@ -343,6 +363,12 @@ struct qldpc_graph {
     long long relabel_stats[4] = {0, 0, 0, 0};  // bank excess before / after, busiest-bank cycles before / after
     std::vector<int> part_row0;             // V2 split: first layout row of each part (+ m)
     int fpl_class_off[qldpc::FPL_CLASSES + 1] = {};  // frame-per-lane: rows by length class (GraphTables::fpl_rows)
+    // error estimation: the row-ELL adjacency on the host (GraphTables::ell_col /
+    // row_deg), a hash of it (a plan's row table belongs to one adjacency) and
+    // the row table without a plan (row_d is row_deg itself there: left empty)
+    std::vector<int32_t> h_ell_col, h_row_deg;
+    uint64_t adjacency = 0;
+    qldpc::EstTable est;
     std::vector<std::unique_ptr<qldpc::DeviceGraph>> devs;
 };
 

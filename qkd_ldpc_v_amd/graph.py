@@ -404,6 +404,82 @@ class Graph:
                                              _dp(bits), _dp(key_out), _stream_ptr(stream, dev)),
               "qldpc_extract_key_device")
 
+    # ---- error estimation at the reconciliation stage ----
+    def estimate_classes(self, plan: "RatePlan | None" = None):
+        """(degree, rows), int32 each: the distinct effective degrees of the
+        informative check rows, ascending, and their row counts
+        (qldpc_estimate_classes; host only).  Empty: nothing can be estimated."""
+        ph = None if plan is None else plan.handle
+        cnt = ctypes.c_int32(0)
+        check(lib().qldpc_estimate_classes(self._g, ph, 0, ctypes.byref(cnt), None, None), "qldpc_estimate_classes")
+        deg, rows = np.empty(cnt.value, np.int32), np.empty(cnt.value, np.int32)
+        check(lib().qldpc_estimate_classes(self._g, ph, cnt.value, ctypes.byref(cnt), ptr(deg), ptr(rows)),
+              "qldpc_estimate_classes")
+        return deg, rows
+
+    def qber_from_weight(self, weight, plan: "RatePlan | None" = None, q_min: float = 1e-4, q_max: float = 0.25,
+                         frames_per_weight: int = 1):
+        """(qber, log_p), float64 each, from syndrome weights (qldpc_qber_from_weight;
+        host only).  frames_per_weight = F: each weight is a sum over F frames."""
+        w = np.ascontiguousarray(weight, np.int64).reshape(-1)
+        q, lp = np.empty(w.size, np.float64), np.empty(w.size, np.float64)
+        check(lib().qldpc_qber_from_weight(self._g, None if plan is None else plan.handle, int(w.size), ptr(w),
+                                           int(frames_per_weight), float(q_min), float(q_max), ptr(q), ptr(lp)),
+              "qldpc_qber_from_weight")
+        return q, lp
+
+    def estimate_qber(self, keys: np.ndarray, syndrome: np.ndarray, plan: "RatePlan | None" = None,
+                      q_min: float = 1e-4, q_max: float = 0.25):
+        """Bob, before the decode (qldpc_estimate_qber_batch): (qber float64,
+        log_p float64, weight int32), [batch] each, from his keys and the
+        received syndromes."""
+        k, batch = self._host_keys(keys, plan)
+        syn = np.ascontiguousarray(syndrome, np.uint8)
+        if syn.ndim == 1:
+            syn = syn[None, :]
+        if syn.shape != (batch, self.m):
+            raise ValueError(f"expected syndrome ({batch},{self.m})")
+        w = np.empty(batch, np.int32)
+        q, lp = np.empty(batch, np.float64), np.empty(batch, np.float64)
+        check(lib().qldpc_estimate_qber_batch(self._g, None if plan is None else plan.handle, batch, ptr(k), ptr(syn),
+                                              float(q_min), float(q_max), ptr(w), ptr(q), ptr(lp)),
+              "qldpc_estimate_qber_batch")
+        return q, lp, w
+
+    def corrected_errors(self, keys: np.ndarray, bits: np.ndarray, plan: "RatePlan | None" = None) -> np.ndarray:
+        """Bob, after the decode (qldpc_corrected_errors_batch): int32 [batch],
+        the key positions at which his key differs from the decoded frame."""
+        k, batch = self._host_keys(keys, plan)
+        b = np.ascontiguousarray(bits, np.uint8)
+        if b.ndim == 1:
+            b = b[None, :]
+        if b.shape != (batch, self.n):
+            raise ValueError(f"expected bits ({batch},{self.n})")
+        err = np.empty(batch, np.int32)
+        check(lib().qldpc_corrected_errors_batch(self._g, None if plan is None else plan.handle, batch, ptr(k), ptr(b),
+                                                 ptr(err)), "qldpc_corrected_errors_batch")
+        return err
+
+    def estimate_qber_device(self, key, syndrome, weight=None, qber=None, log_p=None, plan: "RatePlan | None" = None,
+                             q_min: float = 1e-4, q_max: float = 0.25, stream=None, device: int | None = None) -> None:
+        """Bob: weight int32, qber float64 and log_p float64 [batch] (each
+        optional, not all three missing) from key [batch, n] and the received
+        syndrome [batch, m].  log_p can go to reconcile_device on the same stream."""
+        dev = key.device.index if device is None else device
+        check(lib().qldpc_estimate_qber_device(
+            self._g, None if plan is None else plan.handle, dev, int(key.shape[0]), _dp(key), _dp(syndrome),
+            float(q_min), float(q_max), _dp(weight), _dp(qber), _dp(log_p), _stream_ptr(stream, dev)),
+            "qldpc_estimate_qber_device")
+
+    def corrected_errors_device(self, key, bits, errors, plan: "RatePlan | None" = None, stream=None,
+                                device: int | None = None) -> None:
+        """errors int32 [batch] = the key positions at which key [batch, n]
+        differs from the decoded frames bits [batch, n]."""
+        dev = key.device.index if device is None else device
+        check(lib().qldpc_corrected_errors_device(self._g, None if plan is None else plan.handle, dev,
+                                                  int(key.shape[0]), _dp(key), _dp(bits), _dp(errors),
+                                                  _stream_ptr(stream, dev)), "qldpc_corrected_errors_device")
+
     # ---- blind reconciliation: disclosure rounds for the frames that failed ----
     @staticmethod
     def _round_lists(plan, batch, frames, disc):
