@@ -86,6 +86,15 @@ def split_k2_w16():  # 2 parts of 16 waves, 12 scratch slots
 
 
 @functools.lru_cache(maxsize=None)
+def long_split():
+    """2 parts of 16 waves at an odd n >= 32768: the smallest split shape whose
+    one-workgroup-per-frame kernels (parties, blind, select, estimate) launch
+    1024 threads, with a partial last key word, wave ballot and code byte
+    (row degrees 15..16)."""
+    return Q.regular_code(33001, 6600, 3, 1)
+
+
+@functools.lru_cache(maxsize=None)
 def base_2000x400():
     return random_code(2000, 400, [2, 3], 3)
 
@@ -182,7 +191,7 @@ def _plan(variant, lanes, epl, split, debug=None):
 CODES = {
     "reg44": reg44, "reg44_full": reg44_full, "hybrid_dv4_lds": hybrid_dv4_lds,
     "hybrid_dv4_global": hybrid_dv4_global, "split_k4": split_k4, "split_k2_w8": split_k2_w8,
-    "split_k2_w16": split_k2_w16, "degree1_rows": degree1_rows, "short_rows": short_rows,
+    "split_k2_w16": split_k2_w16, "long_split": long_split, "degree1_rows": degree1_rows, "short_rows": short_rows,
     "row_starts_32": row_starts_32,
     "long_row32": lambda: long_row(32), "long_row33": lambda: long_row(33), "long_row40": lambda: long_row(40),
     "long_row41": lambda: long_row(41), "degree300_bit": degree300_bit, "degree510_bit": degree510_bit,
@@ -201,6 +210,7 @@ PLANS = {
     "split_k4": _plan("v2_split", 2048, 30, (4, 512, 0), (64, 40, 0, 0, 4)),
     "split_k2_w8": _plan("v2_split", 1024, 42, (2, 512, 12), (32, 40, 12, 0, 2)),
     "split_k2_w16": _plan("v2_split", 2048, 45, (2, 1024, 12), (32, 40, 12, 0, 2)),
+    "long_split": _plan("v2_split", 2048, 49, (2, 1024, 12), (32, 40, 12, 0, 2)),
     "degree1_rows": _plan("v2", 256, 24, (1, 256, 0), (4, 40, 0, 0, 1)),
     "short_rows": _plan("v2", 1024, 8, (1, 1024, 0), (16, 40, 0, 0, 1)),
     "row_starts_32": _plan("v2", 128, 32, (1, 128, 0), (2, 40, 0, 0, 1)),

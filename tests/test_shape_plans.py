@@ -63,6 +63,9 @@ def test_cases_cover_the_shapes_they_were_written_for():
     assert [P[c]["split"]["parts"] for c in ("split_k2_w8", "split_k2_w16", "split_k4_isolated", "split_k4")] == \
         [2, 2, 3, 4]
     assert P["split_k2_w8"]["split"]["part_lanes"] == 512 and P["split_k2_w16"]["split"]["part_lanes"] == 1024
+    # test_gpu_long_frames.py: split frames of an odd n at which the per-frame kernels launch 1024 threads
+    H = S.long_split()
+    assert P["long_split"]["split"]["parts"] == 2 and H.n >= 32768 and H.n % 2 == 1
     assert P["long_row32"]["debug"]["waves"] == 3
     assert [P[f"long_row{d}"]["variant"] for d in (33, 40, 41)] == ["reg_lds", "reg_lds", "glb_lds"]
 
